@@ -12,6 +12,10 @@ configs[2]). `--clients 100000` is configs[1]. The CPU baseline is configs[0] ex
 
     python bench.py --gpus N --steps K --warmup W
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps and prints the line. `--full` adds what the headline does
+not need: the recorded warm-up and the output checks, the real protocol's crawls, the CPU baselines.
+`--dump-outputs DIR` writes the last timed step's result as DIR/<name>.npy (dump_outputs).
 """
 from __future__ import annotations
 
@@ -628,7 +632,7 @@ def gc_bench(args, world, rank, local_rank, dist):
     ands = tests * (bits - 1)
     aes_per_test = (2 * bits + 1) + 12 * (bits - 1)   # labels + 8 (garble) + 4 (eval) per AND
     cpu = None
-    if rank == 0 and not args.no_cpu_baseline:
+    if rank == 0 and args.full and not args.no_cpu_baseline:
         from oracle import oracle as O
         O.build()
         m = min(G * N, 1 << 18)
@@ -953,6 +957,44 @@ def load_pmc(config: str):
     return allp.get(config)
 
 
+DUMP_MAX_BYTES = 64 << 20     # --dump-outputs: every file together
+DUMP_SAMPLE_SEED = 0xD0C5     # the fixed sample of a result too large for that
+
+
+def dump_outputs(out_dir: str, res):
+    """--dump-outputs: the SimResult the last timed step handed back (sim_crawl, record off), as float .npy
+    files, in the order the caller receives it:
+      level_children, level_kept  [levels]          float64  children evaluated / kept per level
+      final_paths                 [F, d, levels]    float32  each heavy hitter's path bits
+      final_values                [F]               float64  its value (count; fe mode: v0 - v1)
+      final_value_limbs           [F, 10]           float64  the same value exactly, 32-bit limbs, low first
+      final_index                 [F]               float64  the row of res.final each entry above is
+    Every heavy hitter is written unless that passed DUMP_MAX_BYTES; then a fixed seeded sample of them, in
+    the caller's order (final_index names the rows)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    lc = np.asarray(res.level_children, np.float64)
+    lk = np.asarray(res.level_kept, np.float64)
+    F = len(res.final)
+    idx = np.arange(F)
+    if F:
+        row_bytes = 4 * sum(len(dim) for dim in res.final[0].path) + 8 * 12
+        room = max(1, (DUMP_MAX_BYTES - lc.nbytes - lk.nbytes - 1024 * 6) // row_bytes)
+        if F > room:
+            idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(F, size=int(room), replace=False))
+    rows = [res.final[int(k)] for k in idx]
+    paths = np.array([r.path for r in rows], np.float32) if rows else np.zeros((0, 0, 0), np.float32)
+    values = np.array([float(int(r.value)) for r in rows], np.float64)
+    limbs = np.array([[(int(r.value) >> (32 * j)) & 0xFFFFFFFF for j in range(10)] for r in rows],
+                     np.float64).reshape(len(rows), 10)
+    arrays = {"level_children": lc, "level_kept": lk, "final_paths": paths, "final_values": values,
+              "final_value_limbs": limbs, "final_index": idx.astype(np.float64)}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    log(f"dump-outputs: {len(arrays)} arrays, {sum(a.nbytes for a in arrays.values())} B, "
+        f"{len(rows)} of {F} heavy hitters -> {out_dir}")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -1031,7 +1073,22 @@ def main():
     ap.add_argument("--no-protocol-crawl", action="store_true",
                     help="skip the real protocol's crawl (GC + OT + real base OTs every level) that follows the "
                          "headline's timed region on the zipf workload")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: the recorded warm-up crawls and the output checks against them and "
+                         "the 1M golden, the real protocol's crawls (--no-protocol-crawl, --no-protocol-circuit, "
+                         "--protocol-ss-k) and the CPU baselines (--no-cpu-baseline, --no-cpu-sizes; also "
+                         "--workload gc's CPU leg). A plain run sets up, warms up, times the steps and prints "
+                         "the line with those fields null")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned to its caller as "
+                         "DIR/<name>.npy (float32 / float64; see dump_outputs); the zipf / coords crawl on one GPU")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1 (the timed steps)")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
+    if args.dump_outputs and (args.workload not in ("zipf", "coords") or args.gpus != 1):
+        ap.error("--dump-outputs writes the zipf / coords crawl's result on one GPU")
     if args.rehearse_rccl:
         args.rehearse = True
 
@@ -1158,13 +1215,15 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    # the warm-up crawls record every level's counts (D2H per level; untimed): the output the timed steps
-    # and the protocol crawl are checked against
+    # --full: the warm-up crawls record every level's counts (D2H per level; untimed): the output the timed
+    # steps and the protocol crawl are checked against. A plain run warms up with the timed step itself
     res_ref = None
     for _ in range(args.warmup):
-        res_ref = step(record=True)
+        res_ref = step(record=args.full)
+    if not args.full:
+        res_ref = None
     barrier()
-    log(f"[rank {rank}] warm-up done ({args.warmup} recorded crawls)")
+    log(f"[rank {rank}] warm-up done ({args.warmup} {'recorded ' if args.full else ''}crawls)")
     c0.reset_stats()
     c1.reset_stats()
     t0 = time.perf_counter()
@@ -1189,7 +1248,9 @@ def main():
         a = torch.tensor([ar_us or 0.0], dtype=torch.float64)
         dist.all_reduce(a, op=dist.ReduceOp.MAX)
         ar_us_max = float(a.item()) if ar_us is not None else None
-    run_proto = args.workload == "zipf" and args.gc == "none" and not args.no_protocol_crawl
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, res)
+    run_proto = args.full and args.workload == "zipf" and args.gc == "none" and not args.no_protocol_crawl
     if res_ref is None and run_proto:   # no warm-up: one recorded crawl after the timed region
         res_ref = step(record=True)
     ref_sig = crawl_sig(res_ref) if res_ref is not None else None
@@ -1283,6 +1344,7 @@ def main():
             "scaling": "strong",
             "vs_baseline": None,
             "dtype": "u32",
+            "full": args.full,
             "data": ("synthetic: seeded Zipf workload shaped like leader.rs (num_sites strings + 8-bit augmentation), "
                      "keys by GPU keygen, resident in HBM before the timed region"
                      if args.workload == "zipf" else
@@ -1348,7 +1410,7 @@ def main():
             out["measured_valu_peak_tops"] = r.value / 1e12
             fhh.lib().fhh_microbench(local_rank, 1, ctypes.byref(r))
             out["measured_lds_peak_gbps"] = r.value / 1e9
-        if world == 1 and not args.no_cpu_baseline and args.workload == "zipf":
+        if args.full and world == 1 and not args.no_cpu_baseline and args.workload == "zipf":
             out["cpu_baseline"] = cpu_baseline(args)
         else:
             out["cpu_baseline"] = None

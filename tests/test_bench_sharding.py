@@ -88,7 +88,9 @@ def test_bench_two_rank_rehearsal_equals_one_rank():
     heavy hitters, and the JSON line must aggregate over both ranks."""
     import random
     import sys as _sys
-    common = ["--clients", "20000", "--data-len", "128", "--steps", "1", "--warmup", "1", "--no-cpu-baseline"]
+    # --full: the protocol crawl asserted below runs only there
+    common = ["--clients", "20000", "--data-len", "128", "--steps", "1", "--warmup", "1", "--full",
+              "--no-cpu-baseline"]
     one = _bench_line([_sys.executable, "-u", "bench.py", *common])
     port = str(29600 + random.randrange(300))
     two = _bench_line([_sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
