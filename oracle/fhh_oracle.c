@@ -523,6 +523,136 @@ uint64_t orc_prg_stream_u64(const uint8_t seed[16], uint64_t pos) {
     return v;
 }
 
+/* Search for seeds whose PrgStream rejects (FE::from_rng redraws) at a chosen draw: the fixture
+ * tests/golden/sketch_reject_seeds.json (made by tests/golden/make_sketch_reject_seeds.py; the
+ * suite never runs this). Candidate `c` is the seed LE64(mix64(2c)) || LE64(mix64(2c + 1)) — two
+ * SplitMix64 outputs — so a rerun over the same counters finds the same seeds. For every candidate
+ * in [counter_start, counter_start + n_candidates) and every pos[k] (ascending): keystream block
+ * pos >> 1, half pos & 1 as a little-endian u64 masked to 62 bits, hit when >= p (about 2^-32
+ * each). Hits go to hit_counter / hit_pos / hit_val in no particular order (the caller sorts);
+ * returns the number of hits found, of which the first max_hits are stored. */
+void orc_reject_seed_of(uint64_t c, uint8_t seed[16]) {
+    const uint64_t lo = mix64(2 * c), hi = mix64(2 * c + 1);
+    for (int i = 0; i < 8; i++) {
+        seed[i] = (uint8_t)(lo >> (8 * i));
+        seed[8 + i] = (uint8_t)(hi >> (8 * i));
+    }
+}
+
+#if defined(__x86_64__)
+#define NI_EXPAND_STEP(k, rcon)                                            \
+    do {                                                                   \
+        __m128i t = _mm_aeskeygenassist_si128(k, rcon);                    \
+        t = _mm_shuffle_epi32(t, 0xff);                                    \
+        k = _mm_xor_si128(k, _mm_slli_si128(k, 4));                        \
+        k = _mm_xor_si128(k, _mm_slli_si128(k, 4));                        \
+        k = _mm_xor_si128(k, _mm_slli_si128(k, 4));                        \
+        k = _mm_xor_si128(k, t);                                           \
+    } while (0)
+
+__attribute__((target("aes,sse4.1"))) static inline void ni_key_expand(__m128i k, __m128i rk[11]) {
+    rk[0] = k;
+    NI_EXPAND_STEP(k, 0x01); rk[1] = k;
+    NI_EXPAND_STEP(k, 0x02); rk[2] = k;
+    NI_EXPAND_STEP(k, 0x04); rk[3] = k;
+    NI_EXPAND_STEP(k, 0x08); rk[4] = k;
+    NI_EXPAND_STEP(k, 0x10); rk[5] = k;
+    NI_EXPAND_STEP(k, 0x20); rk[6] = k;
+    NI_EXPAND_STEP(k, 0x40); rk[7] = k;
+    NI_EXPAND_STEP(k, 0x80); rk[8] = k;
+    NI_EXPAND_STEP(k, 0x1b); rk[9] = k;
+    NI_EXPAND_STEP(k, 0x36); rk[10] = k;
+}
+
+/* the draws (both halves of each of nb keystream blocks) of one candidate, AES-NI */
+__attribute__((target("aes,sse4.1"))) static void reject_draws_ni(uint64_t c, const uint64_t* blocks, uint32_t nb,
+                                                                  uint64_t* draws /*[nb][2]*/) {
+    __m128i rk[11];
+    ni_key_expand(_mm_set_epi64x((long long)mix64(2 * c + 1), (long long)mix64(2 * c)), rk);
+    for (uint32_t k = 0; k < nb; k++) {
+        /* BE128(block): the low 8 counter bytes reversed into the register's high half */
+        __m128i x = _mm_set_epi64x((long long)__builtin_bswap64(blocks[k]), 0);
+        x = _mm_xor_si128(x, rk[0]);
+        for (int r = 1; r < 10; r++) x = _mm_aesenc_si128(x, rk[r]);
+        x = _mm_aesenclast_si128(x, rk[10]);
+        draws[2 * k] = (uint64_t)_mm_cvtsi128_si64(x);
+        draws[2 * k + 1] = (uint64_t)_mm_extract_epi64(x, 1);
+    }
+}
+#endif
+
+static void reject_draws_generic(uint64_t c, const uint64_t* blocks, uint32_t nb, uint64_t* draws) {
+    uint8_t seed[16], rk[176], ks[16];
+    orc_reject_seed_of(c, seed);
+    key_expand(seed, rk);
+    for (uint32_t k = 0; k < nb; k++) {
+        uint8_t ctr[16] = {0};
+        for (int i = 0; i < 8; i++) ctr[15 - i] = (uint8_t)(blocks[k] >> (8 * i));
+        aes128_encrypt_rk(rk, ctr, ks);
+        for (int h = 0; h < 2; h++) {
+            uint64_t v = 0;
+            for (int i = 0; i < 8; i++) v |= (uint64_t)ks[8 * h + i] << (8 * i);
+            draws[2 * k + h] = v;
+        }
+    }
+}
+
+/* draw `pos` of candidate c as the search computes it (the tests compare it with orc_prg_stream_u64) */
+uint64_t orc_reject_search_draw(uint64_t c, uint64_t pos) {
+    oracle_init();
+    const uint64_t block = pos >> 1;
+    uint64_t draws[2];
+#if defined(__x86_64__)
+    if (orc_aes_ni_available()) reject_draws_ni(c, &block, 1, draws);
+    else
+#endif
+        reject_draws_generic(c, &block, 1, draws);
+    return draws[pos & 1];
+}
+
+#define ORC_REJECT_MAX_POS 64
+uint64_t orc_find_reject_seed(const uint64_t* pos, uint32_t n_pos, uint64_t counter_start, uint64_t n_candidates,
+                              uint64_t* hit_counter, uint64_t* hit_pos, uint64_t* hit_val, uint64_t max_hits,
+                              int nthreads) {
+    oracle_init();
+    if (n_pos == 0 || n_pos > ORC_REJECT_MAX_POS) return 0;
+    uint64_t blocks[ORC_REJECT_MAX_POS];
+    uint32_t slot[ORC_REJECT_MAX_POS], nb = 0;           /* pos[k] -> draws[slot[k]] */
+    for (uint32_t k = 0; k < n_pos; k++) {
+        if (nb == 0 || blocks[nb - 1] != (pos[k] >> 1)) blocks[nb++] = pos[k] >> 1;
+        slot[k] = 2 * (nb - 1) + (uint32_t)(pos[k] & 1);
+    }
+    const int use_ni = orc_aes_ni_available();
+    uint64_t n_hits = 0;
+    if (nthreads <= 0) nthreads = omp_get_max_threads();
+#pragma omp parallel for schedule(static) num_threads(nthreads)
+    for (int64_t i = 0; i < (int64_t)n_candidates; i++) {
+        const uint64_t c = counter_start + (uint64_t)i;
+        uint64_t draws[2 * ORC_REJECT_MAX_POS];
+#if defined(__x86_64__)
+        if (use_ni) reject_draws_ni(c, blocks, nb, draws);
+        else
+#endif
+            reject_draws_generic(c, blocks, nb, draws);
+        for (uint32_t k = 0; k < n_pos; k++) {
+            const uint64_t v = draws[slot[k]] & FE_MASK;
+            if (v >= FE_P) {
+#pragma omp critical(fhh_reject_hit)
+                {
+                    if (n_hits < max_hits) {
+                        hit_counter[n_hits] = c;
+                        hit_pos[n_hits] = pos[k];
+                        hit_val[n_hits] = v;
+                    }
+                    n_hits++;
+                }
+            }
+        }
+    }
+    (void)use_ni;
+    return n_hits;
+}
+
 /* FE::from_rng (field.rs:252-264 + fastfield.rs:125-139): redraw until the low 62 bits are
  * below p. Returns the FE val; *pos advances past the draws used. */
 static uint64_t fe_from_stream(const uint8_t rk[176], uint64_t* pos, uint8_t ks[16], uint64_t* ks_block) {

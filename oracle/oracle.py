@@ -526,6 +526,38 @@ def prg_stream_u64(seed: bytes, pos: int) -> int:
     return int(lib().orc_prg_stream_u64(_p(s), ctypes.c_uint64(pos)))
 
 
+def reject_seed_of(counter: int) -> bytes:
+    """Candidate seed `counter` of find_reject_seed: LE64(SplitMix64(2c)) || LE64(SplitMix64(2c + 1))."""
+    out = np.zeros(16, np.uint8)
+    lib().orc_reject_seed_of(ctypes.c_uint64(counter), _p(out))
+    return out.tobytes()
+
+
+def reject_search_draw(counter: int, pos: int) -> int:
+    """Stream draw `pos` of candidate `counter` through the search's own (AES-NI) code path."""
+    f = lib().orc_reject_search_draw
+    f.restype = ctypes.c_uint64
+    return int(f(ctypes.c_uint64(counter), ctypes.c_uint64(pos)))
+
+
+def find_reject_seed(positions, counter_start: int, n_candidates: int, nthreads: int = 0):
+    """Every (counter, pos, value) with counter in [counter_start, counter_start + n_candidates) and
+    pos in `positions` whose seed reject_seed_of(counter) draws a 62-bit value >= p at stream draw
+    `pos` (FE::from_rng would redraw there), sorted by counter then pos. About 2^-32 per candidate and
+    position: the fixture generator's search (tests/golden/make_sketch_reject_seeds.py), never run by
+    the suite beyond a few thousand candidates."""
+    pos = np.array(sorted(set(int(q) for q in positions)), np.uint64)
+    assert 0 < pos.size <= 64
+    cap = 4096
+    hc, hp, hv = (np.zeros(cap, np.uint64) for _ in range(3))
+    f = lib().orc_find_reject_seed
+    f.restype = ctypes.c_uint64
+    n = int(f(_p(pos, u64p), ctypes.c_uint32(pos.size), ctypes.c_uint64(counter_start), ctypes.c_uint64(n_candidates),
+              _p(hc, u64p), _p(hp, u64p), _p(hv, u64p), ctypes.c_uint64(cap), ctypes.c_int(nthreads)))
+    assert n <= cap, "more hits than the buffer holds: search fewer candidates per call"
+    return sorted((int(hc[i]), int(hp[i]), int(hv[i])) for i in range(n))
+
+
 u32p = ctypes.POINTER(ctypes.c_uint32)
 
 
@@ -558,7 +590,9 @@ def fe255_op(op: str, a: int, b: int = 0) -> int:
 
 def sketch_fe255(seeds: np.ndarray, x: np.ndarray, kx: np.ndarray, nthreads: int = 0) -> np.ndarray:
     """sketch_at_last (sketch.rs:202-245), U = FieldElm: x / kx [n][nodes][8] u32 LE limbs ->
-    [n][6][8] canonical {r_x, r2_x, r_kx, rand1, rand2, rand3}."""
+    [n][6][8] canonical {r_x, r2_x, r_kx, rand1, rand2, rand3}. Limbs >= p (any value below 2^256)
+    are accepted, as the reference's lazy BigUint products are (tests/test_sketch_edges.py compares
+    them with Python ints)."""
     seeds = np.ascontiguousarray(seeds, np.uint8)
     x = np.ascontiguousarray(x, np.uint32)
     kx = np.ascontiguousarray(kx, np.uint32)
@@ -618,7 +652,13 @@ def sketch_fe(seeds: np.ndarray, x: np.ndarray, kx: np.ndarray, nthreads: int = 
 
 
 def mul_cor_share_fe(sketch6, mac, mac2, triples9) -> np.ndarray:
-    """MulState::new + cor_share (mpc.rs:83-158) per key."""
+    """MulState::new + cor_share (mpc.rs:83-158) per key.
+
+    Input domain: FE vals in the reference's lazy representation, i.e. what FE::new / add / mul leave
+    behind — canonical values and up to about 2^62 + 2^30 (one bit-reduce of a u64). The reference's
+    neg computes 2 p - a on the val (fastfield.rs:235-242) and underflows for a > 2 p, so from about
+    2^63 up this restatement (like the text it restates) no longer equals the arithmetic mod p; the
+    tests use Python ints as the reference for arbitrary u64 words (tests/test_sketch_edges.py)."""
     n = sketch6.shape[0]
     out = np.zeros((n, 6), np.uint64)
     for i in range(n):
@@ -632,7 +672,10 @@ def mul_cor_share_fe(sketch6, mac, mac2, triples9) -> np.ndarray:
 
 
 def mul_out_share_fe(server_idx: int, sketch6, mac, mac2, triples9, cor6) -> np.ndarray:
-    """MulState::out_share (mpc.rs:182-212) per key."""
+    """MulState::out_share (mpc.rs:182-212) per key.
+
+    Input domain: as mul_cor_share_fe — vals up to the reference's lazy representation (about
+    2^62 + 2^30), not arbitrary u64 words (zs = neg(...) underflows above 2 p)."""
     n = sketch6.shape[0]
     out = np.zeros(n, np.uint64)
     for i in range(n):

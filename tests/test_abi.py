@@ -40,6 +40,51 @@ def test_host_only_entry_points(fhh):
     assert fv[0].value == P2 - 3
 
 
+def test_keep_values_any_u64(fhh):
+    """fhh_keep_values on any u64 representation on both sides (FE::new semantics): a < b wraps
+    around, values equal mod p, thresholds 0 and >= p, against Python ints"""
+    from fuzzyheavyhitters_amd.collection import KeyCollection
+    P = fhh.FE_P
+    words = [0, 1, P - 1, P, P + 1, 2**62 - 1, 2**62, 2**62 + 2**30, 2**63 - 1, 2**63, 2 * P, 2 * P + 1, 3 * P,
+             2**64 - 2, 2**64 - 1]
+    v0 = [a for a in words for _ in words] + [5, P + 5, 3 * P + 5, 2, 0]
+    v1 = [b for _ in words for b in words] + [2 * P + 5, 5, P + 5, 3, 4 * P]
+    for thr in (0, 1, 2, 100, P - 1, P, P + 1, 2 * P + 2, 2**63, 2**64 - 1):
+        keep = KeyCollection.keep_values(10, thr, v0, v1)
+        assert list(keep) == [(a - b) % P >= thr % P for a, b in zip(v0, v1)], f"threshold {thr}"
+    assert list(KeyCollection.keep_values(10, 0, v0, v1)) == [True] * len(v0)
+    # equal mod p -> v = 0: kept only by a threshold that is 0 mod p
+    assert list(KeyCollection.keep_values(10, 1, [5, P + 5, 0], [2 * P + 5, 5, 4 * P])) == [False] * 3
+    assert list(KeyCollection.keep_values(10, P, [5, P + 5, 0], [2 * P + 5, 5, 4 * P])) == [True] * 3
+
+
+def test_keep_values_last_and_final_values_edges(fhh):
+    """fhh_keep_values_last / fhh_final_values on 10-limb values up to 2^320 - 1, around multiples of
+    p = 2^255 - 19: k p + delta on both sides (a - b negative included), thresholds 0, 1 and
+    2^32 - 1 against differences with high limbs set, against Python ints"""
+    from fuzzyheavyhitters_amd.collection import KeyCollection, Result
+    P2 = fhh.FE255_P
+    top = 1 << 320
+    vals = [k * P2 + d for k in (0, 1, 2, 3, 1000, 2**64, 2**65 - 40) for d in (-1, 0, 1, 18, 19)]
+    vals = [v for v in vals if 0 <= v < top] + [top - 1, 2**256 - 1, 2**256, 2**255]
+    assert len(vals) == 38 and max(vals) == top - 1 and (2**65 - 40) * P2 + 19 in vals
+    a = [x for x in vals for _ in vals]
+    b = [y for _ in vals for y in vals]
+    diff = [(x - y) % P2 for x, y in zip(a, b)]
+    assert any(x % P2 < y % P2 for x, y in zip(a, b)) and any(d >> 224 for d in diff)
+    fv = KeyCollection.final_values([Result([[True]], x) for x in a], [Result([[True]], y) for y in b])
+    assert [r.value for r in fv] == diff
+    for thr in (0, 1, 2, 19, 2**32 - 1):
+        keep = KeyCollection.keep_values_last(10, thr, a, b)
+        assert list(keep) == [d >= thr for d in diff], f"threshold {thr}"
+    # small differences on both sides of each threshold, from operands many multiples of p apart
+    for thr in (1, 2**32 - 1):
+        xs = [7 * P2 + thr - 1, 2**64 * P2 + thr, thr + 1, 1000 * P2 + 2**32]
+        ys = [3 * P2, 0, (2**65 - 40) * P2, 2 * P2 + 1]
+        keep = KeyCollection.keep_values_last(10, thr, xs, ys)
+        assert list(keep) == [(x - y) % P2 >= thr for x, y in zip(xs, ys)] == [False, True, True, True]
+
+
 def test_create_fails_cleanly_without_gpu(fhh):
     import torch
     if torch.cuda.is_available():
