@@ -722,6 +722,7 @@ struct PartyState {
     uint64_t c_off = 0, level_C = 0, covered = 0;
     uint32_t level_id = 0;
     bool level_last = false;
+    uint32_t level_form = 0;    // the level's first chunk's form: its storage (partials or vals) serves every chunk
     uint64_t C = 0, n = 0, npad = 0, nw = 0, tests = 0, m1 = 0, m2 = 0;
     uint32_t bits = 0, mask = 0, per2 = 1;
     uint32_t s[2][4] = {};      // garbler: the OT-extension sender's base choice words per OT kind
@@ -782,9 +783,14 @@ int party_begin(fhh_ctx* ctx, int role, uint64_t child_begin, uint64_t child_cou
                    P.covered != b))
         return ctx->fail(FHH_E_STATE, "party: chunk at child " + std::to_string(b) + " does not follow the level's " +
                                           "finished children (" + std::to_string(P.covered) + ")");
+    // the level's storage (the fused partials or vals) follows the form and is set up by the first chunk only
+    if (b != 0 && P.level_form != form)
+        return ctx->fail(FHH_E_STATE, "party: chunk at child " + std::to_string(b) + " has form " + std::to_string(form) +
+                                          ", the level's first chunk had form " + std::to_string(P.level_form));
     P.role = role;
     P.step = 0;
     P.last = last;
+    if (b == 0) P.level_form = form;
     P.level_id = ctx->level;
     P.level_last = last;
     P.level_C = LC;
@@ -1226,7 +1232,7 @@ int fhh_party_node_sums(fhh_ctx* ctx, void* sums_a, void* sums_b) {
         if (rc) return rc;
         std::vector<const void*> v((size_t)S, nullptr);
         std::vector<PartyState*> fused_shards;
-        int last = -1;
+        int last = -1, fused = -1;
         for (int k = 0; k < S; k++) {
             fhh_ctx* sh = nullptr;
             uint64_t nk = 0;
@@ -1240,11 +1246,15 @@ int fhh_party_node_sums(fhh_ctx* ctx, void* sums_a, void* sums_b) {
                                                   "'s OTs are not finished for every child of the level");
             if (last >= 0 && last != (int)P->last) return ctx->fail(FHH_E_STATE, "party_node_sums: shards disagree");
             last = P->last;
+            // one path for all: the fused host partials, or the stored values (a shard of the other kind has
+            // nothing valid in the buffer that path reads)
+            if (fused >= 0 && fused != (int)P->lfused) return ctx->fail(FHH_E_STATE, "party_node_sums: shards disagree");
+            fused = P->lfused;
             v[(size_t)k] = P->vals.p;
             fused_shards.push_back(P);
         }
         if (last < 0) return ctx->fail(FHH_E_STATE, "party_node_sums: no shard holds clients");
-        if (!fused_shards.empty() && fused_shards[0]->lfused) {   // r06: the shards' host partials, summed
+        if (fused == 1) {   // r06: the shards' host partials, summed
             const uint64_t LC = fused_shards[0]->level_C;
             std::vector<uint64_t> h(LC * 2, 0);
             for (PartyState* P : fused_shards) {

@@ -622,8 +622,14 @@ int fhh_gt_cot_ring32_host(fhh_ctx* ctx, uint64_t n, uint32_t bits, const uint8_
  * (FHH_COT_FE255: 2 OTs per test). The circuit is fhh_gc_cot_host's (the garbler's string and mask
  * folded in). gc at the FE levels, 2d <= 4: the table's rows 1 .. 2^(2d) - 1, 8 B each, SoA
  * [row][tests]; otherwise [tables (bits-1) x 2 | y 8 B (FE levels) | decode 1 B] per test; tests =
- * C x n child-major; u = the OT receiver's [128][m padded to 8192 / 128] blocks;
- * y1 0 B; u2 / y2: 0 B at the FE levels, FieldElm level: U and 16 B per OT. Each server's node values
+ * C x n child-major; u = the OT receiver's U as its kernels leave it, opaque to the caller (move the
+ * bytes, do not index them): R = 128 / k rows (k = ot_ss_k, 1 for IKNP) of mp / 128 16-B blocks, mp = m
+ * padded to 8192, TILE-MAJOR since r06 — block c of row i at byte 16 ((c / 4) 4 R + 4 i + c % 4), 16 mp / k
+ * bytes — and for k > 1 the SoftSpoken GGM corrections [R][k][2][16] (4096 B) straight after it;
+ * y1 0 B; u2 / y2: 0 B at the FE levels, FieldElm level: U (as u1) and 16 B per OT. A follow-on chunk
+ * (child_begin != 0) must keep the form of the level's first chunk (FHH_E_STATE otherwise: the level's
+ * storage follows the form), and the shards of a multi-device ctx must run a level in one form
+ * (fhh_party_node_sums: "shards disagree"). Each server's node values
  * (the garbler's r1 = v + mask, the evaluator's share output) stay on its device; fhh_party_node_sums sums them: non-last
  * level sums [C] canonical FE, last level [C][10] unreduced + [C][8] canonical FieldElm (the
  * frontier_last values). For a multi-device ctx run each shard (fhh_shard_ctx) with its own channel,

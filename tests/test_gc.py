@@ -420,19 +420,37 @@ def test_oracle_garbled_table_ring32_functional(oracle, bits):
         assert tr["msgs"].shape == fe["msgs"].shape and (rows > 0).any()
 
 
+GRID_STRIDE = "grid-stride"
+
+
+def _grid_stride_n():
+    """The smallest batch whose tile-major table launch (one wave per 512-test tile, 16 waves per
+    workgroup, at most one workgroup per CU) sends its workgroups round the grid-stride loop again: 16 CUs + 2
+    tiles, the last one partial (37 live tests)."""
+    import ctypes
+    from fuzzyheavyhitters_amd._lib import lib
+    cus, name = ctypes.c_int(), ctypes.create_string_buffer(64)
+    assert lib().fhh_device_info(0, name, 64, ctypes.byref(cus)) == 0 and cus.value > 0
+    return 512 * (16 * cus.value + 1) + 37
+
+
 @pytest.mark.gpu
-@pytest.mark.parametrize("n,bits", [(1, 2), (65, 1), (1000, 2), (4097, 2)])
+@pytest.mark.parametrize("n,bits", [(1, 2), (65, 1), (1000, 2), (4097, 2), (GRID_STRIDE, 2)])
 def test_gpu_garbled_table_ring32_bit_exact(oracle, n, bits):
     """r06: fhh_gt_cot_ring32_host (the tile-major table kernels with Z_2^32 shares) = the oracle chain bit for
-    bit: every 4-B message and both parties' values; gb - ev = eq mod 2^32."""
+    bit: every 4-B message and both parties' values; gb - ev = eq mod 2^32. The grid-stride case (more
+    tiles than 16 per CU: the loop's second pass) runs one mask and counter setting."""
     import fuzzyheavyhitters_amd as fhh
     from fuzzyheavyhitters_amd import gc
+    big = n == GRID_STRIDE
+    if big:
+        n = _grid_stride_n()
     rng = np.random.default_rng(n * 11 + bits)
     g, e = _cases(rng, n, bits)
     seeds = rng.integers(0, 256, (128, 2, 16), dtype=np.uint8)
     s = _colour_s(rng)
     kc = fhh.KeyCollection(8, 1)
-    for mask, ctr in ((0, 0), (1, 256)):
+    for mask, ctr in (((1, 256),) if big else ((0, 0), (1, 256))):
         tr = gc.table_cot(kc, g, e, mask, seeds, s, gate_base=13, ctr_off=ctr, ring32=True)
         etr = _oracle_table_chain_ring32(oracle, g, e, mask, seeds, s, gate_base=13, ctr_off=ctr)
         for k in ("ev_zero", "ev_active", "msgs", "gb_share", "ev_share"):
@@ -458,22 +476,29 @@ def test_gpu_crawl_with_ring32_table_equals_plain(gc_mode, ss_k):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("n,bits", [(1, 2), (65, 1), (1000, 2), (777, 3), (4097, 4)])
+@pytest.mark.parametrize("n,bits", [(1, 2), (65, 1), (513, 1), (1000, 1), (1000, 2), (777, 3), (4097, 4),
+                                    (GRID_STRIDE, 2)])
 def test_gpu_garbled_table_bit_exact(oracle, n, bits):
     """fhh_gt_cot_host (labels OT + k_gt_garble + k_gt_eval) = the oracle chain bit for bit: zero and
-    active labels, every row's message, both parties' node values; gb - ev = eq mod p."""
+    active labels, every row's message, both parties' node values; gb - ev = eq mod p. The grid-stride
+    case (more tiles than 16 per CU: the tile-major kernels' second pass through their loop, the last
+    tile partial) runs one mask and counter setting, with the Python-int check on both ends' slices."""
     import fuzzyheavyhitters_amd as fhh
     from fuzzyheavyhitters_amd import gc
+    big = n == GRID_STRIDE
+    if big:
+        n = _grid_stride_n()
     rng = np.random.default_rng(n * 7 + bits)
     g, e = _cases(rng, n, bits)
     seeds = rng.integers(0, 256, (128, 2, 16), dtype=np.uint8)
     s = _colour_s(rng)
     kc = fhh.KeyCollection(8, 1)
-    for mask, ctr in ((0, 0), (1, 256)):
+    for mask, ctr in (((1, 256),) if big else ((0, 0), (1, 256))):
         tr = gc.table_cot(kc, g, e, mask, seeds, s, gate_base=13, ctr_off=ctr)
         etr = _oracle_table_chain(oracle, g, e, mask, seeds, s, gate_base=13, ctr_off=ctr)
         for k in ("ev_zero", "ev_active", "msgs", "gb_share", "ev_share"):
             assert np.array_equal(tr[k], etr[k]), k
         eq = (g == e).all(axis=1).astype(np.uint64)
-        assert np.array_equal(((tr["gb_share"].astype(object) - tr["ev_share"].astype(object)) % FE_P)
-                              .astype(np.uint64), eq)
+        sl = np.r_[0:3000, n - 3000:n] if big else np.arange(n)
+        assert np.array_equal(((tr["gb_share"][sl].astype(object) - tr["ev_share"][sl].astype(object)) % FE_P)
+                              .astype(np.uint64), eq[sl])
