@@ -243,6 +243,11 @@ class KeyCollection:
         """Select the k_expand variant (bit-identical outputs, different speed)."""
         self._chk(lib().fhh_set_variant(self._h, variant))
 
+    def set_expand_grid(self, blocks: int):
+        """Tests / diagnostics: run k_expand on `blocks` workgroups (1 .. the variant's own grid)
+        instead of the occupancy-derived grid. `set_variant` drops the override: call it first."""
+        self._chk(lib().fhh_set_expand_grid(self._h, blocks))
+
     def reset_stats(self):
         self._chk(lib().fhh_reset_stats(self._h))
 

@@ -2328,7 +2328,41 @@ int fhh_set_variant(fhh_ctx* ctx, int variant) {
         return ctx->fail(FHH_E_ARG, "set_variant: variant " + std::to_string(variant) +
                                         " is not in this build (it holds 52 and 33; the r01-r03 A/B forms were removed)");
     ctx->variant = variant;
-    ctx->grid = expand_grid(ctx->device, variant);
+    ctx->grid = expand_grid(ctx->device, variant);   // also drops a fhh_set_expand_grid override
+    return FHH_OK;
+}
+
+int fhh_set_expand_grid(fhh_ctx* ctx, int blocks) {
+    CTX_CHECK(ctx);
+    if (ctx->group) return group_each(ctx, fhh_set_expand_grid, blocks);
+    // shrink only: the occupancy value is the most blocks that are resident at once, and the dynamic
+    // heads assume a persistent grid
+    const int full = expand_grid(ctx->device, ctx->variant);
+    if (blocks < 1 || blocks > full)
+        return ctx->fail(FHH_E_ARG, "set_expand_grid: blocks must be in [1, " + std::to_string(full) + "]");
+    ctx->grid = blocks;
+    return FHH_OK;
+}
+
+int fhh_expand_layout(int variant, int grid_blocks, uint32_t njobs, const uint32_t* n_live, uint32_t nw, uint32_t* g,
+                      uint32_t* wpi, uint64_t* items_a, uint64_t* total) {
+    if (variant < 0 || variant >= expand_variant_count() || !expand_threads(variant)) {
+        g_err = "expand_layout: no such variant in this build";
+        return FHH_E_ARG;
+    }
+    if (grid_blocks < 1 || njobs < 1 || njobs > (uint32_t)kMaxJobs || !n_live || nw < 1) {
+        g_err = "expand_layout: bad arguments";
+        return FHH_E_ARG;
+    }
+    // as finalize_launch, k_prune and k_loop_init call it
+    const uint64_t waves = (uint64_t)grid_blocks * (expand_threads(variant) / 64);
+    ItemLayout lay;
+    item_layout(n_live, njobs, nw, expand_max_group(variant), waves, expand_tail_split(variant), lay,
+                expand_max_wpi(variant));
+    if (g) *g = lay.g;
+    if (wpi) *wpi = lay.wpi;
+    if (items_a) *items_a = lay.items_a;
+    if (total) *total = lay.total;
     return FHH_OK;
 }
 

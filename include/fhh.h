@@ -736,6 +736,21 @@ int fhh_set_variant(fhh_ctx* ctx, int variant);
 /* Describe variant: layout name, workgroup size, persistent grid on the current device.
  * Returns FHH_E_ARG for an id not in this build. */
 int fhh_variant_info(int variant, char* name, size_t cap, int* threads, int* grid_per_device);
+/* Test / diagnostic ABI, not a product knob: run k_expand on a persistent grid of `blocks` workgroups
+ * instead of the variant's occupancy-derived one (fhh_variant_info's grid_per_device). k_expand's work
+ * decomposition (entries per item, words per item, static first items, head count) depends only on the
+ * ratio of work to grid waves, so a grid of a few blocks puts a few thousand clients into the regimes
+ * the full grid reaches at 100k-1M clients. Shrinks only: FHH_E_ARG unless 1 <= blocks <= that grid.
+ * Applies to every later launch of the ctx (a pair launch and the device loop take the first ctx's).
+ * fhh_set_variant recomputes the grid and so drops the override: set the variant first. */
+int fhh_set_expand_grid(fhh_ctx* ctx, int blocks);
+/* Test / diagnostic ABI, pure host arithmetic (no GPU): the work decomposition k_expand variant
+ * `variant` gets on a grid of grid_blocks workgroups for a launch of njobs (<= 8) jobs with n_live[k]
+ * live entries each over nw 64-client words — the same function the host launches and the device loop's
+ * kernels call. g = entries per item, wpi = words per item, items_a = bulk items, total = all items
+ * (any output may be NULL). FHH_E_ARG for a variant not in this build or empty shapes. */
+int fhh_expand_layout(int variant, int grid_blocks, uint32_t njobs, const uint32_t* n_live, uint32_t nw, uint32_t* g,
+                      uint32_t* wpi, uint64_t* items_a, uint64_t* total);
 int fhh_reset_stats(fhh_ctx* ctx);
 /* 1 to time every k_expand launch with HIP events (default 1); K > 1 times every K-th launch
  * of the device level loop (a pair of event records costs the stream a few microseconds). */
