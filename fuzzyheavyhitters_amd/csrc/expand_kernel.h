@@ -2,12 +2,8 @@
 // (dim-prefix entry, client, side, direction), with the PRG expand_dir (prg.rs:92-122) as an
 // LDS T-table AES-128 and the MMO feed-forward.
 //
-// The kernel is a template over
-//   Tab   — the LDS T-table layout (how a byte of state becomes a conflict-free ds_read_b32),
-//   NB    — AES blocks per lane kept in flight (4: both sides x both dirs; 2: one side),
-//   THR   — workgroup size,
-// plus a runtime choice of static (grid-stride) or dynamic (atomic work counter) item
-// distribution. fhh_kernels.hip instantiates the variants; fhh_set_variant selects one.
+// The table layouts (how a byte of state becomes a conflict-free ds_read_b32) and the AES forms over
+// them live here; fhh_kernels.hip holds k_expand itself and its two built forms (fhh_set_variant).
 //
 // Every Tab is generic over Ops (perm/load/bfe) so tests/host/aes_ttable_host_test.cpp can
 // instantiate the exact same lookup code on the CPU with emulated v_perm_b32.
@@ -23,24 +19,7 @@ template <int k> __host__ __device__ __forceinline__ uint32_t rotk(uint32_t v) {
 }
 
 // ---- layouts ----------------------------------------------------------------------------
-// A: T0 only, one replica per lane (64), entry stride 256 B (64 KiB). addr = 1 v_perm.
-template <class Ops> struct TabT0R64 {
-    static constexpr int kWords = 256 * 64;
-    static constexpr const char* kName = "T0/64rep/64KiB";
-    __host__ __device__ static uint32_t word(const uint32_t* t0, int i) { return t0[i >> 6]; }
-    __host__ __device__ static void bases(uint32_t lane, uint32_t& b0, uint32_t& b1) { b0 = lane * 4; b1 = 0; }
-    template <int k>
-    __host__ __device__ static uint32_t term(const uint32_t* t, uint32_t b0, uint32_t, uint32_t x) {
-        return rotk<k>(Ops::load(t, Ops::perm(b0, x, lookup_sel(k))));
-    }
-    template <int k>
-    __host__ __device__ static uint32_t last(const uint32_t* t, uint32_t b0, uint32_t, uint32_t x) {
-        return Ops::load(t, Ops::perm(b0, x, lookup_sel(k)));
-    }
-    static constexpr int spos(int) { return 1; }
-};
-
-// B: four tables T0..T3, 32 replicas each (lanes l and l+32 share a replica: they are in
+// Four tables T0..T3, 32 replicas each (lanes l and l+32 share a replica: they are in
 // different ds_read_b32 lane groups), 128 KiB. Region m (64 KiB) holds T_{2m} in bytes
 // [0,128) and T_{2m+1} in [128,256) of each 256-B entry row. No rotations.
 template <class Ops> struct Tab4T32 {
@@ -75,7 +54,8 @@ template <class Ops> struct Tab4T32 {
     static constexpr int spos(int k) { return k; }
 };
 
-// C: T0 only, 32 replicas, entry stride 128 B (32 KiB). addr = bfe + lshl_or (2 VALU).
+// T0 only, 32 replicas, entry stride 128 B (32 KiB). addr = bfe + lshl_or (2 VALU). The sketch's
+// SubWord table (fhh_sketch.hip).
 template <class Ops> struct TabT0R32 {
     static constexpr int kWords = 256 * 32;
     static constexpr const char* kName = "T0/32rep/32KiB";
@@ -92,27 +72,6 @@ template <class Ops> struct TabT0R32 {
     template <int k>
     __host__ __device__ static uint32_t last(const uint32_t* t, uint32_t b0, uint32_t, uint32_t x) {
         return Ops::load(t, addr<k>(b0, x));
-    }
-    static constexpr int spos(int) { return 1; }
-};
-
-// D: T0 and T1 interleaved (32 replicas each, 64 KiB); T2 = rotl16(T0), T3 = rotl16(T1).
-template <class Ops> struct TabT01R32 {
-    static constexpr int kWords = 256 * 64;
-    static constexpr const char* kName = "T0,T1/32rep/64KiB";
-    __host__ __device__ static uint32_t word(const uint32_t* t0, int i) {
-        const uint32_t v = t0[i >> 6];
-        return (i & 63) >= 32 ? rotl32(v, 8) : v;
-    }
-    __host__ __device__ static void bases(uint32_t lane, uint32_t& b0, uint32_t& b1) { b0 = (lane & 31) * 4; b1 = 0; }
-    template <int k>
-    __host__ __device__ static uint32_t term(const uint32_t* t, uint32_t b0, uint32_t, uint32_t x) {
-        const uint32_t v = Ops::load(t, Ops::perm(b0, x, lookup_sel(k)) + 128u * (k & 1));
-        return (k >= 2) ? rotl32(v, 16) : v;
-    }
-    template <int k>
-    __host__ __device__ static uint32_t last(const uint32_t* t, uint32_t b0, uint32_t, uint32_t x) {
-        return Ops::load(t, Ops::perm(b0, x, lookup_sel(k)));
     }
     static constexpr int spos(int) { return 1; }
 };

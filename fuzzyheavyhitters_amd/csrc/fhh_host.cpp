@@ -275,13 +275,7 @@ int prepare_expand(fhh_ctx* ctx, ExpandJob* jobs, uint32_t* njobs) {
         J.npad = (uint32_t)ctx->npad;
         J.nw = (uint32_t)ctx->nw;
         J.group = 1;
-        J.wpi = 1;
         J.item_begin = 0;
-        J.split = J.n_live;
-        J.group_b = 1;
-        J.e_base = 0;
-        J.pad2_ = 0;
-        J.item_begin_b = 0;
     }
     return FHH_OK;
 }
@@ -292,19 +286,12 @@ void finalize_launch(ExpandLaunch& L, int grid, int variant) {
     uint32_t n_live[kMaxJobs] = {};
     for (uint32_t k = 0; k < L.njobs; k++) n_live[k] = L.job[k].n_live;
     ItemLayout lay;
-    item_layout(n_live, L.njobs, L.job[0].nw, expand_max_group(variant), waves,
-                expand_tail_split(variant), lay, expand_max_wpi(variant));
+    item_layout(n_live, L.njobs, L.job[0].nw, expand_max_group(variant), waves, lay, expand_max_wpi(variant));
     L.wpi = lay.wpi;
     for (uint32_t k = 0; k < L.njobs; k++) {
-        ExpandJob& J = L.job[k];
-        J.wpi = lay.wpi;
-        J.group = lay.g;
-        J.group_b = lay.g_b;
-        J.split = lay.split[k];
-        J.item_begin = lay.begin_a[k];
-        J.item_begin_b = lay.begin_b[k];
+        L.job[k].group = lay.g;
+        L.job[k].item_begin = lay.begin[k];
     }
-    L.items_a = lay.items_a;
     L.total_items = lay.total;
 }
 
@@ -1494,7 +1481,6 @@ int sim_crawl_device_loop(fhh_ctx* c0, fhh_ctx* c1, const fhh_sim_config* cfg, u
         pa.grid_waves = grid_waves;
         pa.unit = (uint32_t)c0->nw;
         pa.max_group = expand_max_group(variant);
-        pa.tail_split = expand_tail_split(variant) ? 1u : 0u;
         pa.max_wpi = expand_max_wpi(variant);
         pa.zero_partials = (cfg->mode != 0 && !last) ? B.partials.as<uint64_t>() : nullptr;
         pa.ring32 = ring32 && !last ? 1u : 0u;
@@ -2345,7 +2331,7 @@ int fhh_set_expand_grid(fhh_ctx* ctx, int blocks) {
 }
 
 int fhh_expand_layout(int variant, int grid_blocks, uint32_t njobs, const uint32_t* n_live, uint32_t nw, uint32_t* g,
-                      uint32_t* wpi, uint64_t* items_a, uint64_t* total) {
+                      uint32_t* wpi, uint64_t* total) {
     if (variant < 0 || variant >= expand_variant_count() || !expand_threads(variant)) {
         g_err = "expand_layout: no such variant in this build";
         return FHH_E_ARG;
@@ -2357,11 +2343,9 @@ int fhh_expand_layout(int variant, int grid_blocks, uint32_t njobs, const uint32
     // as finalize_launch, k_prune and k_loop_init call it
     const uint64_t waves = (uint64_t)grid_blocks * (expand_threads(variant) / 64);
     ItemLayout lay;
-    item_layout(n_live, njobs, nw, expand_max_group(variant), waves, expand_tail_split(variant), lay,
-                expand_max_wpi(variant));
+    item_layout(n_live, njobs, nw, expand_max_group(variant), waves, lay, expand_max_wpi(variant));
     if (g) *g = lay.g;
     if (wpi) *wpi = lay.wpi;
-    if (items_a) *items_a = lay.items_a;
     if (total) *total = lay.total;
     return FHH_OK;
 }

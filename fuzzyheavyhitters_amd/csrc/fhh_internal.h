@@ -44,16 +44,7 @@ struct ExpandJob {
     uint32_t npad;
     uint32_t nw;
     uint32_t group;         // entries per work item (CW reuse factor)
-    uint32_t wpi;           // words (64-client units) per work item (item_layout; 1 = one word)
-    uint64_t item_begin;
-    // end-of-launch phase (item_layout): entries [split, n_live) as items of group_b entries,
-    // numbered from item_begin_b after every job's bulk items; e_base = first entry of the
-    // segment an item belongs to (set by the kernel)
-    uint32_t split;
-    uint32_t group_b;
-    uint32_t e_base;
-    uint32_t pad2_;
-    uint64_t item_begin_b;
+    uint64_t item_begin;    // the launch's first item of this job
 };
 
 // Device-resident level loop (fhh_sim_crawl with the GPU loop): the frontier sizes live in
@@ -69,32 +60,23 @@ struct LoopCtl {
     uint32_t C;                 // pending children (F << d)
     uint32_t n_live[kMaxDims];  // live entries per dim (same for both servers)
     uint32_t group;             // entries per work item for the next k_expand
-    uint32_t group_b;           // entries per end-phase item
-    uint32_t wpi;               // words per bulk item (item_layout)
-    uint32_t pad_;
+    uint32_t wpi;               // words per item (item_layout)
     uint64_t item_begin[kMaxJobs];
     uint64_t total_items;
-    uint64_t items_a;           // bulk items of all jobs precede the end-phase items
-    uint64_t item_begin_b[kMaxJobs];
-    uint32_t split[kMaxJobs];
 };
 
 // k_expand work decomposition, shared by the host (finalize_launch) and the device loop
-// (k_prune, k_loop_init). Bulk: items of g entries x one word unit (64 clients), g sized so
-// each wave gets >= 2 items, capped at max_group. A launch ends when its slowest wave finishes
-// its last item, and with 16-entry items that tail averaged 8.7 % of k_expand's time
-// (tools/tail_profile.py). So about one item per wave of work at the end is re-cut as items
-// of g_b = min(g, kTailGroup) entries, dealt after every job's bulk items. The end phase must
-// not outrun the single work counter (≈ 88 dequeues/µs): 4-entry items at 2 per wave did
-// (8 % slower), hence 8 entries and one item per wave.
-// Words per item (max_wpi > 1, no end phase): when the frontier is narrow (d = 2 at data_len 16,
-// or the first levels of any crawl) a group holds only a few entries, so one-word items are too
-// small for the single counter — configs[3] at 1M clients made 62 500 items of ~2.5 entries per
-// level and k_expand ran at the counter's 88 items/µs (25 G blocks/s). A bulk item then spans
+// (k_prune, k_loop_init). An item is g entries x wpi word units (64 clients each), g sized so
+// each wave gets >= 2 items, capped at max_group (the CorWord reuse). Every item of a launch has
+// the same shape: re-cutting the launch's last items smaller (against the wait for the slowest
+// wave) measured no gain.
+// Words per item (max_wpi > 1): when the frontier is narrow (d = 2 at data_len 16, or the first
+// levels of any crawl) a group holds only a few entries, so one-word items are too small for the
+// single counter — configs[3] at 1M clients made 62 500 items of ~2.5 entries per level and
+// k_expand ran at the counter's 88 items/µs (25 G blocks/s). An item then spans
 // wpi = max_group / (entries per group) consecutive words (64-client units), lowered until the
 // launch still has kMwItemsPerWave items per wave; wide levels (groups of ≥ max_group / 2 entries)
 // keep wpi = 1.
-constexpr uint32_t kTailGroup = 8;
 // r05: 4 (was 2) since k_expand draws from 8 per-XCD heads on narrow levels: configs[3] k_expand
 // 0.44 -> 0.47 of the VALU roofline, the d = 1 headline unchanged (profiles/r05/expand_heads/)
 // (r06 A/B, profiles/r06/ab_mw_ipw/: 2 -> 0.459, 8 or 16 -> 0.166 — wpi falls to 1 — against 0.478)
@@ -103,24 +85,20 @@ constexpr uint32_t kTailGroup = 8;
 #endif
 constexpr uint64_t kMwItemsPerWave = FHH_MW_IPW;
 struct ItemLayout {
-    uint32_t g, g_b, wpi;
-    uint64_t items_a, total;
-    uint64_t begin_a[kMaxJobs], begin_b[kMaxJobs];
-    uint32_t split[kMaxJobs];
+    uint32_t g, wpi;
+    uint64_t total;
+    uint64_t begin[kMaxJobs];   // each job's first item
 };
 __host__ __device__ inline void item_layout(const uint32_t* n_live, uint32_t njobs, uint32_t unit, uint32_t max_group,
-                                            uint64_t grid_waves, bool tail_split, ItemLayout& L,
-                                            uint32_t max_wpi = 1) {
+                                            uint64_t grid_waves, ItemLayout& L, uint32_t max_wpi = 1) {
     uint64_t entries = 0;
     for (uint32_t k = 0; k < njobs; k++) entries += n_live[k];
     const uint64_t entry_words = entries * unit;
     uint64_t g = entry_words / (2 * grid_waves);
     g = g < 1 ? 1 : (g > max_group ? max_group : g);
-    const uint64_t gb = g < kTailGroup ? g : kTailGroup;
     L.g = (uint32_t)g;
-    L.g_b = (uint32_t)gb;
     uint64_t wpi = 1;
-    if (max_wpi > 1 && !tail_split) {
+    if (max_wpi > 1) {
         uint64_t groups = 0;
         for (uint32_t k = 0; k < njobs; k++) groups += (n_live[k] + g - 1) / g;
         if (groups) {
@@ -131,46 +109,46 @@ __host__ __device__ inline void item_layout(const uint32_t* n_live, uint32_t njo
         }
     }
     L.wpi = (uint32_t)wpi;
-    const uint64_t units = (unit + wpi - 1) / wpi;   // bulk items per entry group
-    // end-phase entries wanted in all: one item of g_b entries per wave
-    const uint64_t want = (tail_split && gb < g) ? (grid_waves * gb + unit - 1) / unit : 0;
-    for (uint32_t k = 0; k < njobs; k++) {
-        uint32_t split = n_live[k];
-        if (want && entries) {
-            const uint64_t bk = (n_live[k] * want + entries - 1) / entries;   // job's share, rounded up
-            split = bk >= n_live[k] ? 0u : (uint32_t)(n_live[k] - bk);
-        }
-        L.split[k] = split;
-    }
+    const uint64_t units = (unit + wpi - 1) / wpi;   // items per entry group
     uint64_t begin = 0;
     for (uint32_t k = 0; k < njobs; k++) {
-        L.begin_a[k] = begin;
-        begin += units * ((L.split[k] + g - 1) / g);
-    }
-    L.items_a = begin;
-    for (uint32_t k = 0; k < njobs; k++) {
-        L.begin_b[k] = begin;
-        begin += (uint64_t)unit * ((n_live[k] - L.split[k] + gb - 1) / gb);
+        L.begin[k] = begin;
+        begin += units * ((n_live[k] + g - 1) / g);
     }
     L.total = begin;
 }
 
+// One job's item `local` (= item - its begin) of a layout: entry group local / ceil(nw / wpi), words
+// [w0, w1) of chunk local % ceil(nw / wpi), entries [e0, e1) (wpi = 1: group local / nw, word
+// local % nw). k_expand decodes its items with this.
+struct ItemRange {
+    uint32_t w0, w1, e0, e1;
+};
+__host__ __device__ inline ItemRange item_range(uint64_t local, uint32_t n_live, uint32_t nw, uint32_t g, uint32_t wpi) {
+    const uint32_t chunks = (nw + wpi - 1) / wpi;
+    const uint32_t grp = (uint32_t)(local / chunks), w0 = (uint32_t)(local % chunks) * wpi;
+    const uint32_t e0 = grp * g;
+    ItemRange r;
+    r.w0 = w0;
+    r.w1 = w0 + wpi < nw ? w0 + wpi : nw;
+    r.e0 = e0;
+    r.e1 = e0 + g < n_live ? e0 + g : n_live;
+    return r;
+}
+
 // k_expand's dynamic work heads inside fhh_ctx::work_counter (kWorkCounterBytes): two sets of
 // kExpandHeads per-XCD heads (one 64-B line each) by launch parity (the kernel zeroes the next
-// launch's set), then the wave-timeline exit count of the profiling variant; words 0-1 belong to the
-// r01 A/B kernels' re-armed counter (unused since r06)
+// launch's set), from word kExpandSlot0 on; the words before and after them are unused
 constexpr uint32_t kExpandHeads = 8, kExpandSlot0 = 16, kExpandSlotStride = 16;
-constexpr uint32_t kExpandProfSlot = kExpandSlot0 + 2 * kExpandHeads * kExpandSlotStride;
 constexpr size_t kWorkCounterBytes = 2048;
-static_assert((kExpandProfSlot + 1) * 4 <= kWorkCounterBytes, "work counter layout");
+static_assert((kExpandSlot0 + 2 * kExpandHeads * kExpandSlotStride) * 4 <= kWorkCounterBytes, "work counter layout");
 
 struct ExpandLaunch {
     ExpandJob job[kMaxJobs];
     uint32_t njobs;
     uint32_t jobs_per_ctx;      // = d (LoopCtl::n_live index = job % jobs_per_ctx)
     uint64_t total_items;
-    uint64_t items_a;           // host-driven launches: bulk items (== total_items without a tail phase)
-    uint32_t wpi;               // host-driven launches: words per bulk item (item_layout)
+    uint32_t wpi;               // host-driven launches: words per item (item_layout)
     uint32_t seq;               // the counter's launch number (fhh_ctx::expand_seq): k_expand counter slot
     const LoopCtl* ctl;         // non-null: n_live / group / item_begin / total_items from here
 };
@@ -297,7 +275,6 @@ struct PruneArgs {
     uint64_t grid_waves;        // persistent k_expand waves (for the group size)
     uint32_t unit;              // k_expand items per entry group (nw)
     uint32_t max_group;         // entries per item cap
-    uint32_t tail_split;        // item_layout end phase (expand_tail_split)
     uint32_t max_wpi;           // item_layout words-per-item cap (expand_max_wpi)
     // FE levels: k_child_sums_fe adds its client chunks into the partials by atomics, so a prune that
     // completes zeroes them for the next level (a memset node would also run after a sticky
@@ -326,6 +303,9 @@ hipError_t launch_expand(const ExpandLaunch& a, int variant, int grid, uint32_t*
 int expand_variant_count();
 const char* expand_variant_name(int variant);
 int expand_threads(int variant);
+// item_layout's caps for the variant: entries per item, words per item (1: one-word items only)
+uint32_t expand_max_group(int variant);
+uint32_t expand_max_wpi(int variant);
 hipError_t launch_eq_count(const ChildArgs& a, uint64_t* counts, hipStream_t stream);
 hipError_t launch_share_planes(const ChildArgs& a, uint64_t* out, hipStream_t stream);
 // zero: clear partials first (host-driven launches); the device loop's k_prune clears them instead
@@ -360,7 +340,7 @@ int comm_group_allreduce(const std::vector<::fhh_comm*>& comms, const std::vecto
 void comm_abort(::fhh_comm* c);
 int comm_rank(const ::fhh_comm* c);   // the rank given at creation
 // device-resident level loop (fhh_loop.hip); `unit` = items per entry group, `max_group` =
-// entries per item cap (see expand_unit)
+// entries per item cap (expand_max_group)
 hipError_t launch_prune(const PruneArgs& a, hipStream_t stream);
 // IKNP / ALSZ OT extension (row f1's OT): m OTs of 16-B messages; base OTs given as key schedules
 // (the sender's are those of k_i^{s_i}). Bit matrices are [128 rows][mp / 128] uint4 blocks, read per
@@ -541,29 +521,5 @@ hipError_t launch_deal_triples_fe(uint64_t n, uint32_t levels, uint64_t seed, ui
 hipError_t launch_sketch_fe255(const Sketch255Args& a, hipStream_t stream);
 hipError_t launch_mul_fe255(const Mul255Args& a, hipStream_t stream);
 hipError_t launch_verify_fe255(const Verify255Args& a, hipStream_t stream);
-
-// entries per work item (CW reuse and counter traffic vs. end-of-level tail): variant 29 is
-// variant 3 drawing the next item one entry ahead; 30 / 31 are variant 3 with up to 16 / 32
-// entries per item; 32 / 33 store child seeds nontemporally with up to 8 / 16 entries per item;
-// 34 / 35 are 33 / 32 with the sibling-pair AES (aes0_mmo_pair); 36 is 34 + wave timeline;
-// 37 / 38 are 34 / 36 with the end-of-launch phase of small items (item_layout); 39 / 40 are
-// 34 at 768 / 512 threads (3 / 2 waves per SIMD: a VGPR budget of 168 / 256 lets the
-// scheduler keep more T-table lookups in flight per wave); 41 is 39 drawing the next item ahead;
-// 42 is 34 with the next entry's seeds prefetched under the current entry's AES; 43 / 44 are
-// DIAGNOSTIC builds of 34 that store no / only the dir-0 child seeds (HBM-write A/B; their states
-// are incomplete by design and no product path selects them); 45 / 46 / 47 / 48 are the hybrid:
-// 34 with the last 2 / 4 / 6 / 8 of each workgroup's 16 waves running the pair-sliced VALU AES
-// (expand_ps.h) on the same items; 49 runs every wave as a VALU wave (the test variant that
-// pins expand_item_ps: in 45-48 which items the VALU waves take depends on timing); 50 is 34 with
-// ordinary (write-back) child-seed stores instead of nontemporal ones (the power-bound A/B)
-inline uint32_t expand_max_group(int variant) {
-    return (variant == 30 || variant == 33 || variant == 34 || (variant >= 36 && variant <= 52))
-               ? 16u : variant == 31 ? 32u : 8u;
-}
-// 51 is 34 with multi-word items on narrow levels and each wave's first item taken statically
-// (k_expand FLAGS bit 12), the only variants whose item_layout may set wpi > 1 are 51 and 52 (51 with
-// nontemporal parent-seed loads, FLAGS bit 13)
-inline uint32_t expand_max_wpi(int variant) { return variant == 51 || variant == 52 ? 16u : 1u; }
-inline bool expand_tail_split(int variant) { return variant == 37 || variant == 38; }
 
 }  // namespace fhh

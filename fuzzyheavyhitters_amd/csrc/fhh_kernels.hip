@@ -20,7 +20,9 @@
 // hybrid, the earlier T-table variants) and their generated AES programs were removed in r06; they are
 // in git history at commit 78c7ebe (fhh_expand_bs.hip, expand_ps.h, aes_bs_gen.h, aes_ps_gen.h,
 // tools/gen_aes_bs.py, tools/gen_aes_ps.py). The build holds the product
-// variant 52 and the generic-AES variant 33 the parity suite compares it with.
+// variant 52 and the generic-AES variant 33 the parity suite compares it with; the kernel switches
+// only the removed forms used (draw-ahead, prefetch, wave timeline, end-of-launch phase, store
+// diagnostics) are in history at commit 531b030.
 
 namespace fhh {
 
@@ -36,29 +38,24 @@ __device__ __forceinline__ void fill_table(uint32_t* tbl) {
 }
 
 // --------------------------------------------------------------------------------------
-// k_expand: one wave = 64 consecutive clients of one dim-j prefix group. Per entry and
-// lane: 2 sides x 2 directions = 4 AES blocks (NB = 4 in lockstep, or NB = 2 per side).
-// CorWords of (level, dim, side, client) are loaded once per work item and reused for
-// `group` entries. Work items are dealt grid-stride (static) or from an atomic counter.
+// k_expand: one wave = 64 consecutive clients (one word) of one dim-j prefix group. Per entry
+// and lane: 2 sides x 2 directions = 4 AES blocks in lockstep. CorWords of (level, dim, side,
+// client) are loaded once per word of a work item and reused for the item's entries. Work items
+// (item_layout) are drawn from atomic heads.
 // --------------------------------------------------------------------------------------
-// ahead != nullptr: draw the next work item from the counter right after the first entry's
-// seeds have been consumed, so the (contended) atomic completes under that entry's AES instead
-// of stalling the next item's start (vmcnt retires in issue order, so it must not precede the
-// loads this item waits on)
 typedef uint32_t v4u32_t __attribute__((ext_vector_type(4)));
+using ExpandTab = Tab4T32<DevOpsX>;
+constexpr int kExpandBlock = 1024;   // threads per workgroup: 16 waves share the 128 KiB of tables
 
-// NT: child seeds are written with the nontemporal hint — they are read again only at the next
-// level, and 1.3 GB per launch left dirty in L2 costs a writeback at every kernel boundary
-// STORE (diagnostic A/B only, never a product variant): 0 = every child seed, 1 = none (a store
-// guarded by an output value that never occurs, so the AES stays live), 2 = dir-0 children only
-// (about the half that survives a prune) — the HBM-write share of k_expand's time and power
-// (entry group g, word w): clients 64 w .. 64 w + 63 of entries [e_base + g group, + group).
+// Word w (clients 64 w .. 64 w + 63) of entries [e_begin, e_end) of job J.
+// Child seeds are written with the nontemporal hint: they are read again only at the next level,
+// and 1.3 GB per launch left dirty in L2 costs a writeback at every kernel boundary.
+// PAIR: sibling-pair AES (dir 0 / dir 1 share rounds 1-2, aes0_mmo_pair) instead of the generic one.
 // NTL: parent seeds read with the nontemporal hint (each is read once per level; the CWs are
-// re-read by every entry group of the level and should keep the L2)
-template <class Tab, int NB, bool NT = false, bool PAIR = false, int STORE = 0, bool NTL = false>
-__device__ __forceinline__ void expand_item_wg(const ExpandJob& J, uint32_t w, uint32_t g, const uint32_t* tbl,
-                                               uint32_t lane, uint32_t b0, uint32_t b1, uint32_t* ahead = nullptr,
-                                               uint32_t* next = nullptr) {
+// re-read by every entry group of the level and should keep the L2).
+template <bool PAIR, bool NTL>
+__device__ __forceinline__ void expand_word(const ExpandJob& J, uint32_t w, uint32_t e_begin, uint32_t e_end,
+                                            const uint32_t* tbl, uint32_t lane, uint32_t b0, uint32_t b1) {
     const uint32_t c = w * 64 + lane;
     const size_t npad = J.npad, nw = J.nw;
 
@@ -73,122 +70,24 @@ __device__ __forceinline__ void expand_item_wg(const ExpandJob& J, uint32_t w, u
         for (int b = 0; b < 4; b++) cwp[s][b] = J.cw_bits[((krow + s) * 4 + b) * nw + w];
     }
 
-    const uint32_t e_begin = J.e_base + g * J.group;
-    const uint32_t e_end = min(e_begin + J.group, J.n_live);
     for (uint32_t e = e_begin; e < e_end; e++) {
         const uint32_t src = J.live[e];
-#pragma unroll
-        for (int s0 = 0; s0 < 2; s0 += NB / 2) {
-            uint32_t blk[NB][4];      // index (s - s0)*2 + dir
-            uint64_t tw[NB / 2], yw[NB / 2];
-            uint64_t pb[NB], py[NB];  // PRG control bits (tau.bits / tau.y_bits) as ballot planes
-#pragma unroll
-            for (int q = 0; q < NB / 2; q++) {
-                const int s = s0 + q;
-                uint4 sd;
-                if constexpr (NTL) {
-                    const v4u32_t v = __builtin_nontemporal_load(
-                        reinterpret_cast<const v4u32_t*>(J.src_seed + ((size_t)src * 2 + s) * npad + c));
-                    sd = make_uint4(v[0], v[1], v[2], v[3]);
-                } else {
-                    sd = J.src_seed[((size_t)src * 2 + s) * npad + c];
-                }
-                tw[q] = J.src_t[((size_t)src * 2 + s) * nw + w];
-                yw[q] = J.src_y[((size_t)src * 2 + s) * nw + w];
-                const uint32_t sw[4] = {sd.x, sd.y, sd.z, sd.w};
-#pragma unroll
-                for (int dir = 0; dir < 2; dir++) {
-                    prg_ctr(sw, dir, blk[q * 2 + dir]);
-                    uint32_t bit, ybit;
-                    prg_ctrl_bits(blk[q * 2 + dir][0], dir, bit, ybit);
-                    pb[q * 2 + dir] = __ballot(bit);
-                    py[q * 2 + dir] = __ballot(ybit);
-                }
-            }
-            if (ahead && e == e_begin && s0 == 0 && lane == 0) *next = atomicAdd(ahead, 1u);
-
-            if constexpr (PAIR) aes0_mmo_pair<DevOpsX, Tab, NB>(blk, tbl, b0, b1);
-            else aes0_mmo_tab<DevOpsX, Tab, NB>(blk, tbl, b0, b1);
-
-#pragma unroll
-            for (int q = 0; q < NB / 2; q++) {
-                const int s = s0 + q;
-                const uint32_t tmask = 0u - (uint32_t)((tw[q] >> lane) & 1);   // if state.bit
-#pragma unroll
-                for (int dir = 0; dir < 2; dir++) {
-                    const uint32_t* o = blk[q * 2 + dir];
-                    uint4 out;
-                    out.x = o[0] ^ (cw[s].x & tmask);
-                    out.y = o[1] ^ (cw[s].y & tmask);
-                    out.z = o[2] ^ (cw[s].z & tmask);
-                    out.w = o[3] ^ (cw[s].w & tmask);
-                    const size_t de = (size_t)(2 * e + dir) * 2 + s;
-                    const bool st = STORE == 0 || (STORE == 2 && dir == 0) ||
-                                    (STORE == 1 && (out.x ^ out.y ^ out.z ^ out.w) == 0x5EED5EEDu && out.x == 0);
-                    if (!st) {
-                    } else if constexpr (NT) {
-                        v4u32_t o4 = {out.x, out.y, out.z, out.w};
-                        __builtin_nontemporal_store(o4, reinterpret_cast<v4u32_t*>(J.dst_seed + de * npad + c));
-                    } else {
-                        J.dst_seed[de * npad + c] = out;
-                    }
-                    if (lane == 0) {
-                        // new_bit = tau.bits[dir] ^ (t & cw.bits[dir]);
-                        // new_y = tau.y_bits[dir] ^ (t & cw.y_bits[dir]) ^ y   (ibDCF.rs:211-219)
-                        J.dst_t[de * nw + w] = pb[q * 2 + dir] ^ (tw[q] & cwp[s][dir]);
-                        J.dst_y[de * nw + w] = py[q * 2 + dir] ^ (tw[q] & cwp[s][2 + dir]) ^ yw[q];
-                    }
-                }
-            }
-        }
-    }
-}
-
-template <class Tab, int NB, bool NT = false, bool PAIR = false, int STORE = 0>
-__device__ __forceinline__ void expand_item(const ExpandJob& J, uint64_t local, const uint32_t* tbl, uint32_t lane,
-                                            uint32_t b0, uint32_t b1, uint32_t* ahead = nullptr,
-                                            uint32_t* next = nullptr) {
-    expand_item_wg<Tab, NB, NT, PAIR, STORE>(J, (uint32_t)(local % J.nw), (uint32_t)(local / J.nw), tbl, lane, b0, b1,
-                                             ahead, next);
-}
-
-// NB = 4 with the next entry's seeds / t / y prefetched while the current entry's AES runs.
-template <class Tab, bool NT = false, bool PAIR = false>
-__device__ __forceinline__ void expand_item_pf(const ExpandJob& J, uint64_t local, const uint32_t* tbl, uint32_t lane,
-                                               uint32_t b0, uint32_t b1) {
-    const uint32_t w = (uint32_t)(local % J.nw);
-    const uint32_t g = (uint32_t)(local / J.nw);
-    const uint32_t c = w * 64 + lane;
-    const size_t npad = J.npad, nw = J.nw;
-    const size_t krow = (size_t)J.level * J.K + 2 * J.dim;
-    uint4 cw[2];
-    uint64_t cwp[2][4];
-#pragma unroll
-    for (int s = 0; s < 2; s++) {
-        cw[s] = J.cw_seed[(krow + s) * npad + c];
-#pragma unroll
-        for (int b = 0; b < 4; b++) cwp[s][b] = J.cw_bits[((krow + s) * 4 + b) * nw + w];
-    }
-    const uint32_t e_begin = J.e_base + g * J.group;
-    const uint32_t e_end = min(e_begin + J.group, J.n_live);
-    if (e_begin >= e_end) return;
-    uint4 sd[2];
-    uint64_t tw[2], yw[2];
-    {
-        const uint32_t src = J.live[e_begin];
+        uint32_t blk[4][4];     // index s * 2 + dir
+        uint64_t tw[2], yw[2];
+        uint64_t pb[4], py[4];  // PRG control bits (tau.bits / tau.y_bits) as ballot planes
 #pragma unroll
         for (int s = 0; s < 2; s++) {
-            sd[s] = J.src_seed[((size_t)src * 2 + s) * npad + c];
+            uint4 sd;
+            if constexpr (NTL) {
+                const v4u32_t v = __builtin_nontemporal_load(
+                    reinterpret_cast<const v4u32_t*>(J.src_seed + ((size_t)src * 2 + s) * npad + c));
+                sd = make_uint4(v[0], v[1], v[2], v[3]);
+            } else {
+                sd = J.src_seed[((size_t)src * 2 + s) * npad + c];
+            }
             tw[s] = J.src_t[((size_t)src * 2 + s) * nw + w];
             yw[s] = J.src_y[((size_t)src * 2 + s) * nw + w];
-        }
-    }
-    for (uint32_t e = e_begin; e < e_end; e++) {
-        uint32_t blk[4][4];
-        uint64_t pb[4], py[4];
-#pragma unroll
-        for (int s = 0; s < 2; s++) {
-            const uint32_t sw[4] = {sd[s].x, sd[s].y, sd[s].z, sd[s].w};
+            const uint32_t sw[4] = {sd.x, sd.y, sd.z, sd.w};
 #pragma unroll
             for (int dir = 0; dir < 2; dir++) {
                 prg_ctr(sw, dir, blk[s * 2 + dir]);
@@ -198,102 +97,67 @@ __device__ __forceinline__ void expand_item_pf(const ExpandJob& J, uint64_t loca
                 py[s * 2 + dir] = __ballot(ybit);
             }
         }
-        const uint64_t ctw[2] = {tw[0], tw[1]}, cyw[2] = {yw[0], yw[1]};
-        if (e + 1 < e_end) {   // prefetch (wave-uniform branch)
-            const uint32_t src = J.live[e + 1];
-#pragma unroll
-            for (int s = 0; s < 2; s++) {
-                sd[s] = J.src_seed[((size_t)src * 2 + s) * npad + c];
-                tw[s] = J.src_t[((size_t)src * 2 + s) * nw + w];
-                yw[s] = J.src_y[((size_t)src * 2 + s) * nw + w];
-            }
-        }
-        if constexpr (PAIR) aes0_mmo_pair<DevOpsX, Tab, 4>(blk, tbl, b0, b1);
-        else aes0_mmo_tab<DevOpsX, Tab, 4>(blk, tbl, b0, b1);
+
+        if constexpr (PAIR) aes0_mmo_pair<DevOpsX, ExpandTab, 4>(blk, tbl, b0, b1);
+        else aes0_mmo_tab<DevOpsX, ExpandTab, 4>(blk, tbl, b0, b1);
+
 #pragma unroll
         for (int s = 0; s < 2; s++) {
-            const uint32_t tmask = 0u - (uint32_t)((ctw[s] >> lane) & 1);
+            const uint32_t tmask = 0u - (uint32_t)((tw[s] >> lane) & 1);   // if state.bit
 #pragma unroll
             for (int dir = 0; dir < 2; dir++) {
                 const uint32_t* o = blk[s * 2 + dir];
-                uint4 out;
-                out.x = o[0] ^ (cw[s].x & tmask);
-                out.y = o[1] ^ (cw[s].y & tmask);
-                out.z = o[2] ^ (cw[s].z & tmask);
-                out.w = o[3] ^ (cw[s].w & tmask);
+                const v4u32_t out = {o[0] ^ (cw[s].x & tmask), o[1] ^ (cw[s].y & tmask), o[2] ^ (cw[s].z & tmask),
+                                     o[3] ^ (cw[s].w & tmask)};
                 const size_t de = (size_t)(2 * e + dir) * 2 + s;
-                if constexpr (NT) {
-                    v4u32_t o4 = {out.x, out.y, out.z, out.w};
-                    __builtin_nontemporal_store(o4, reinterpret_cast<v4u32_t*>(J.dst_seed + de * npad + c));
-                } else {
-                    J.dst_seed[de * npad + c] = out;
-                }
+                __builtin_nontemporal_store(out, reinterpret_cast<v4u32_t*>(J.dst_seed + de * npad + c));
                 if (lane == 0) {
-                    J.dst_t[de * nw + w] = pb[s * 2 + dir] ^ (ctw[s] & cwp[s][dir]);
-                    J.dst_y[de * nw + w] = py[s * 2 + dir] ^ (ctw[s] & cwp[s][2 + dir]) ^ cyw[s];
+                    // new_bit = tau.bits[dir] ^ (t & cw.bits[dir]);
+                    // new_y = tau.y_bits[dir] ^ (t & cw.y_bits[dir]) ^ y   (ibDCF.rs:211-219)
+                    J.dst_t[de * nw + w] = pb[s * 2 + dir] ^ (tw[s] & cwp[s][dir]);
+                    J.dst_y[de * nw + w] = py[s * 2 + dir] ^ (tw[s] & cwp[s][2 + dir]) ^ yw[s];
                 }
             }
         }
     }
 }
 
-// Wave timeline of the profiling variant (FLAGS bit 3, tools/tail_profile.py): per launch and
-// wave {start after the LDS fill, exit, items} in 100 MHz s_memrealtime ticks, written by lane 0
-// with vector stores into a caller buffer of g_wprof_cap launches; the last wave out bumps the
-// launch index (the same exit detection that re-arms the work counter).
-__device__ uint64_t* g_wprof_buf = nullptr;
-__device__ uint32_t g_wprof_cap = 0;
-__device__ uint32_t g_wprof_launch = 0;
-
-// FLAGS: bit 0 = draw the next item one entry ahead, bit 1 = nontemporal child-seed stores,
-// bit 2 = sibling-pair AES (dir 0 / dir 1 share rounds 1-2, aes0_mmo_pair), bit 3 = wave timeline,
-// bit 4 = decode the end-phase items of item_layout (only the variants that lay them out:
-// the extra decode state made the 1024-thread kernel spill), bits 7-11 were the r02 hybrid's VALU
-// waves (removed in r06),
-// bit 12 = MW: a bulk item may span wpi consecutive words (item_layout, narrow levels), and each
-// wave's first item is its wave index instead of a counter draw (the counter then hands out items
-// from nwaves on: 4 096 simultaneous first draws cost ≈ 46 µs at the counter's 88 per µs)
-template <class Tab, int NB, int THR, int MINW, bool PF = false, int FLAGS = 0>
-__global__ __launch_bounds__(THR, MINW) void k_expand(ExpandLaunch a, uint32_t* work_counter) {
-    constexpr bool AHEAD = (FLAGS & 1) != 0;
-    constexpr bool NT = (FLAGS & 2) != 0;
-    constexpr bool PAIR = (FLAGS & 4) != 0;
-    constexpr bool PROF = (FLAGS & 8) != 0;
-    constexpr bool TAIL = (FLAGS & 16) != 0;
-    constexpr int STORE = (FLAGS >> 5) & 3;   // diagnostic variants 43 / 44 only
-    constexpr bool MW = (FLAGS & 4096) != 0;
-    constexpr bool NTL = (FLAGS & 8192) != 0;   // bit 13: nontemporal parent-seed loads (MW path)
-    static_assert(!(MW && (AHEAD || TAIL || PF)), "MW: plain dynamic items only");
-    static_assert(((FLAGS >> 7) & 31) == 0, "the hybrid VALU waves were removed in r06");
-    __shared__ uint32_t tbl[Tab::kWords];
+// The two built forms differ in three switches (any other combination is simply not instantiated):
+// PAIR / NTL: expand_word's AES form and parent-seed loads.
+// MW: an item may span wpi consecutive words (item_layout, narrow levels), and each wave's first
+// item is its wave index instead of a counter draw (the counter then hands out items from nwaves
+// on: 4 096 simultaneous first draws cost ≈ 46 µs at the counter's 88 per µs). Without MW every
+// item is one word and every item is drawn.
+template <bool PAIR, bool MW, bool NTL>
+__global__ __launch_bounds__(kExpandBlock, 1) void k_expand(ExpandLaunch a, uint32_t* work_counter) {
+    __shared__ uint32_t tbl[ExpandTab::kWords];
     __shared__ uint32_t s_drained;   // bit h: a wave of this workgroup found head h dry
-    for (int i = threadIdx.x; i < Tab::kWords; i += THR) tbl[i] = Tab::word(c_T0.v, i);
+    for (int i = threadIdx.x; i < ExpandTab::kWords; i += kExpandBlock) tbl[i] = ExpandTab::word(c_T0.v, i);
     if (threadIdx.x == 0) s_drained = 0;
     __syncthreads();
-    uint64_t prof_t0 = 0, prof_items = 0;
-    if constexpr (PROF) prof_t0 = wall_clock64();
 
     const uint32_t lane = threadIdx.x & 63;
     uint32_t b0, b1;
-    Tab::bases(lane, b0, b1);
-    const uint64_t wpb = THR / 64;
+    ExpandTab::bases(lane, b0, b1);
+    const uint64_t wpb = kExpandBlock / 64;
     const uint64_t nwaves = (uint64_t)gridDim.x * wpb;
     // sizes: kernel arguments (host-driven crawl) or LoopCtl (device-resident loop)
     const LoopCtl* ctl = a.ctl;
     const uint64_t total = ctl ? (ctl->abort ? 0 : ctl->total_items) : a.total_items;
+    const uint32_t wpi = MW ? __builtin_amdgcn_readfirstlane(ctl ? ctl->wpi : a.wpi) : 1u;
     // Dynamic items come from H heads, one per XCD (blocks b and b + 8 share an XCD: one word
     // saturates at ≈88 dequeues/µs, 8 per-XCD heads do not), head h handing out items
     // draw_base + h + H·v. A block draws from its own head first, then from the others once they
     // run dry. The heads of a launch alternate between two sets by launch number: the first block
     // zeroes the other set for the next launch on the stream (the previous launch, done, used it),
     // so there is no exit count (4 096 same-address exit atomics alone cost ≈46 µs per launch).
-    constexpr uint32_t H = AHEAD ? 1u : kExpandHeads;
-    uint32_t* heads = work_counter ? work_counter + kExpandSlot0 + (a.seq & 1) * kExpandHeads * kExpandSlotStride : nullptr;
-    if (work_counter && blockIdx.x == 0 && threadIdx.x < kExpandHeads)
-        atomicExch(work_counter + kExpandSlot0 + ((a.seq + 1) & 1) * kExpandHeads * kExpandSlotStride +
+    constexpr uint32_t H = kExpandHeads;
+    uint32_t* heads = work_counter + kExpandSlot0 + (a.seq & 1) * H * kExpandSlotStride;
+    if (blockIdx.x == 0 && threadIdx.x < H)
+        atomicExch(work_counter + kExpandSlot0 + ((a.seq + 1) & 1) * H * kExpandSlotStride +
                        threadIdx.x * kExpandSlotStride, 0u);
     // (MW: wide levels, one-word items, keep one head — the per-XCD split measured ≈1 % slower there)
-    const uint32_t nh = MW ? (__builtin_amdgcn_readfirstlane(ctl ? ctl->wpi : a.wpi) > 1 ? H : 1u) : H;
+    const uint32_t nh = MW ? (wpi > 1 ? H : 1u) : H;
     const uint32_t home = blockIdx.x & (nh - 1);
     const uint64_t draw_base = MW ? nwaves : 0;   // the first nwaves items are dealt statically (MW)
     // lane 0 draws; bit h of s_drained: a wave of this block found head h dry (its siblings skip it)
@@ -315,18 +179,11 @@ __global__ __launch_bounds__(THR, MINW) void k_expand(ExpandLaunch a, uint32_t* 
         return ((uint64_t)__builtin_amdgcn_readfirstlane((uint32_t)(it >> 32)) << 32) |
                __builtin_amdgcn_readfirstlane((uint32_t)it);
     };
-    uint64_t item = (uint64_t)blockIdx.x * wpb + wave_id_uniform();   // static, MW
-    if (heads && !MW) item = draw();
-    const uint64_t items_a = TAIL ? (ctl ? ctl->items_a : a.items_a) : total;
+    uint64_t item = MW ? (uint64_t)blockIdx.x * wpb + wave_id_uniform() : draw();
     while (item < total) {
-        // bulk items [0, items_a), then the end phase (item_layout): same job order in each
-        const bool tail = TAIL && item >= items_a;
         uint32_t ji = 0;
         if (ctl) {
-            const uint64_t* beg = tail ? ctl->item_begin_b : ctl->item_begin;
-            while (ji + 1 < a.njobs && item >= beg[ji + 1]) ji++;
-        } else if (tail) {
-            while (ji + 1 < a.njobs && item >= a.job[ji + 1].item_begin_b) ji++;
+            while (ji + 1 < a.njobs && item >= ctl->item_begin[ji + 1]) ji++;
         } else {
             while (ji + 1 < a.njobs && item >= a.job[ji + 1].item_begin) ji++;
         }
@@ -335,101 +192,35 @@ __global__ __launch_bounds__(THR, MINW) void k_expand(ExpandLaunch a, uint32_t* 
             J.n_live = ctl->n_live[ji % a.jobs_per_ctx];
             J.group = ctl->group;
             J.item_begin = ctl->item_begin[ji];
-            if constexpr (TAIL) {
-                J.group_b = ctl->group_b;
-                J.split = ctl->split[ji];
-                J.item_begin_b = ctl->item_begin_b[ji];
-            }
         }
-        J.e_base = 0;
-        if constexpr (TAIL) {
-            if (tail) {
-                J.e_base = J.split;
-                J.group = J.group_b;
-                J.item_begin = J.item_begin_b;
-            } else {
-                J.n_live = J.split;
-            }
-        }
-        uint32_t nxt = 0;
-        if constexpr (PROF) prof_items++;
-        if constexpr (MW) {
-            // bulk item = (entry group, chunk of wpi words): local = group * ceil(nw / wpi) + chunk
-            // (wpi = 1 is the one-word item of the other variants: grp = local / nw, w = local % nw)
-            const uint32_t wpi = __builtin_amdgcn_readfirstlane(ctl ? ctl->wpi : a.wpi);
-            const uint64_t local = item - J.item_begin;
-            const uint32_t nwi = (J.nw + wpi - 1) / wpi;
-            const uint32_t grp = (uint32_t)(local / nwi), w0 = (uint32_t)(local % nwi) * wpi, w1 = min(J.nw, w0 + wpi);
-            for (uint32_t w = w0; w < w1; w++)
-                expand_item_wg<Tab, NB, NT, PAIR, STORE, NTL>(J, w, grp, tbl, lane, b0, b1);
-        } else if constexpr (PF) expand_item_pf<Tab, NT, PAIR>(J, item - J.item_begin, tbl, lane, b0, b1);
-        else if constexpr (AHEAD) expand_item<Tab, NB, NT, PAIR, STORE>(J, item - J.item_begin, tbl, lane, b0, b1, heads, &nxt);
-        else expand_item<Tab, NB, NT, PAIR, STORE>(J, item - J.item_begin, tbl, lane, b0, b1);
-        if (heads) {
-            if constexpr (AHEAD) item = (uint64_t)__builtin_amdgcn_readfirstlane(nxt) + draw_base;   // H = 1
-            else item = draw();
-        } else {
-            item += nwaves;
-        }
-    }
-    if constexpr (PROF) {
-        const uint64_t t1 = wall_clock64();
-        const uint32_t L = g_wprof_launch;
-        if (lane == 0 && g_wprof_buf && L < g_wprof_cap) {
-            uint64_t* r = g_wprof_buf + ((uint64_t)L * nwaves + (uint64_t)blockIdx.x * wpb + wave_id_uniform()) * 3;
-            r[0] = prof_t0;
-            r[1] = t1;
-            r[2] = prof_items;
-        }
-    }
-    if constexpr (PROF) {   // the wave timeline's launch index: the last wave out bumps it
-        if (work_counter && lane == 0) {
-            const uint32_t done = atomicAdd(work_counter + kExpandProfSlot, 1u);
-            if (done + 1 == (uint32_t)nwaves) {
-                atomicAdd(&g_wprof_launch, 1u);
-                atomicExch(work_counter + kExpandProfSlot, 0u);
-            }
-        }
+        const ItemRange r = item_range(item - J.item_begin, J.n_live, J.nw, J.group, wpi);
+        for (uint32_t w = r.w0; w < r.w1; w++) expand_word<PAIR, NTL>(J, w, r.e0, r.e1, tbl, lane, b0, b1);
+        item = draw();
     }
 }
 
-// arm the wave timeline: buf = device buffer of cap launches x grid waves x 3 u64 (NULL disarms)
-extern "C" int fhh_wave_profile_arm(int device, uint64_t* buf, uint32_t cap) {
-    if (hipSetDevice(device) != hipSuccess) return FHH_E_HIP;
-    const uint32_t zero = 0;
-    if (hipMemcpyToSymbol(HIP_SYMBOL(g_wprof_buf), &buf, sizeof buf) != hipSuccess ||
-        hipMemcpyToSymbol(HIP_SYMBOL(g_wprof_cap), &cap, sizeof cap) != hipSuccess ||
-        hipMemcpyToSymbol(HIP_SYMBOL(g_wprof_launch), &zero, sizeof zero) != hipSuccess)
-        return FHH_E_HIP;
-    return FHH_OK;
-}
-
-extern "C" int fhh_wave_profile_launches(int device, uint32_t* launches) {
-    if (hipSetDevice(device) != hipSuccess || !launches) return FHH_E_HIP;
-    return hipMemcpyFromSymbol(launches, HIP_SYMBOL(g_wprof_launch), sizeof *launches) == hipSuccess ? FHH_OK : FHH_E_HIP;
-}
-
-// Variant table (fhh_set_variant): id, table layout, blocks per lane, threads, min waves, dynamic
-// items, [prefetch, FLAGS]: 52 is the product default, 33 the generic-AES form the parity suite
-// compares it with (the other ids of r01-r03 were removed in r06).
-#define FHH_EXPAND_VARIANTS(X)                                   \
-    X(33, Tab4T32<DevOpsX>, 4, 1024, 1, true, false, 2)            \
-    X(52, Tab4T32<DevOpsX>, 4, 1024, 1, true, false, 6 | 4096 | 8192)
+// Variant table (fhh_set_variant): id, PAIR, MW, NTL, then item_layout's caps for the form — entries
+// per item (the CorWord reuse against the wait for the launch's slowest wave) and words per item
+// (above 1 only with MW). 52 is the product default, 33 the generic-AES form the parity suite
+// compares it with; every other id is refused.
+#define FHH_EXPAND_VARIANTS(X)      \
+    X(33, false, false, false, 16, 1) \
+    X(52, true, true, true, 16, 16)
 
 struct VariantInfo {
     const void* fn;
     int threads;
-    bool dynamic;
+    uint32_t max_group, max_wpi;
     const char* name;
 };
 
 static VariantInfo variant_info(int v) {
     switch (v) {
-#define FHH_CASE(id, TAB, NB, THR, MINW, DYN, ...) \
-    case id: return VariantInfo{reinterpret_cast<const void*>(&k_expand<TAB, NB, THR, MINW, ##__VA_ARGS__>), THR, DYN, TAB::kName};
+#define FHH_CASE(id, PAIR, MW, NTL, MAXG, MAXW) \
+    case id: return VariantInfo{reinterpret_cast<const void*>(&k_expand<PAIR, MW, NTL>), kExpandBlock, MAXG, MAXW, ExpandTab::kName};
         FHH_EXPAND_VARIANTS(FHH_CASE)
 #undef FHH_CASE
-        default: return VariantInfo{nullptr, 0, false, ""};
+        default: return VariantInfo{nullptr, 0, 0, 0, ""};
     }
 }
 
@@ -442,27 +233,23 @@ hipError_t launch_expand(const ExpandLaunch& a0, int variant, int grid, uint32_t
     if (a0.total_items == 0) return hipSuccess;
     ExpandLaunch a = a0;
     // the head set of this launch is chosen by the sequence's parity, and the launch zeroes the other
-    // set for the next one: the sequence advances only once a dynamic launch has been enqueued, so a
-    // refused or failed launch cannot make the next one draw from a set the launch before used up
+    // set for the next one (fhh_create zeroes both): the sequence advances only once a launch has been
+    // enqueued, so a refused or failed launch cannot make the next one draw from a set the launch before
+    // used up
     a.seq = *seq;
-    const VariantInfo vi = variant_info(variant);
-    if (!vi.fn) return hipErrorInvalidValue;
-    const uint64_t wpb = vi.threads / 64;
+    const uint64_t wpb = kExpandBlock / 64;
     const uint64_t blocks_needed = (a.total_items + wpb - 1) / wpb;
     // device-resident loop: the item count is only known on the device -> full persistent grid
     const int g = a.ctl ? grid : (int)(blocks_needed < (uint64_t)grid ? blocks_needed : (uint64_t)grid);
-    // dynamic mode: the counter slot of launch a.seq must be zero at launch (the previous
-    // k_expand on this counter zeroed it; fhh_create zeroes both)
-    uint32_t* ctr = vi.dynamic ? work_counter : nullptr;
     switch (variant) {
-#define FHH_CASE(id, TAB, NB, THR, MINW, DYN, ...) \
-    case id: hipLaunchKernelGGL((k_expand<TAB, NB, THR, MINW, ##__VA_ARGS__>), dim3(g), dim3(THR), 0, stream, a, ctr); break;
+#define FHH_CASE(id, PAIR, MW, NTL, MAXG, MAXW) \
+    case id: hipLaunchKernelGGL((k_expand<PAIR, MW, NTL>), dim3(g), dim3(kExpandBlock), 0, stream, a, work_counter); break;
         FHH_EXPAND_VARIANTS(FHH_CASE)
 #undef FHH_CASE
         default: return hipErrorInvalidValue;
     }
     const hipError_t e = hipGetLastError();
-    if (e == hipSuccess && ctr) ++*seq;
+    if (e == hipSuccess) ++*seq;
     return e;
 }
 
@@ -479,6 +266,8 @@ int expand_grid(int device, int variant) {
 }
 
 int expand_threads(int variant) { return variant_info(variant).threads; }
+uint32_t expand_max_group(int variant) { return variant_info(variant).max_group; }
+uint32_t expand_max_wpi(int variant) { return variant_info(variant).max_wpi; }
 
 // --------------------------------------------------------------------------------------
 // Child-level kernels (one block per child, grid-stride).

@@ -168,16 +168,10 @@ __global__ __launch_bounds__(kPruneThreads) void k_prune(PruneArgs a) {
     const uint32_t njobs = a.nctx * a.njobs_per_ctx;
     for (uint32_t k = 0; k < njobs; k++) job_live[k] = n_live_new[k % a.njobs_per_ctx];
     ItemLayout lay;
-    item_layout(job_live, njobs, a.unit, a.max_group, a.grid_waves, a.tail_split != 0, lay, a.max_wpi);
-    for (uint32_t k = 0; k < njobs; k++) {
-        ctl->item_begin[k] = lay.begin_a[k];
-        ctl->item_begin_b[k] = lay.begin_b[k];
-        ctl->split[k] = lay.split[k];
-    }
+    item_layout(job_live, njobs, a.unit, a.max_group, a.grid_waves, lay, a.max_wpi);
+    for (uint32_t k = 0; k < njobs; k++) ctl->item_begin[k] = lay.begin[k];
     ctl->group = lay.g;
-    ctl->group_b = lay.g_b;
     ctl->wpi = lay.wpi;
-    ctl->items_a = lay.items_a;
     ctl->total_items = lay.total;
     ctl->F = nf;
     ctl->C = nf << d;
@@ -272,21 +266,15 @@ __global__ void k_loop_init(LoopCtl* ctl, uint32_t d, uint32_t unit, uint32_t ma
         pos0[j] = 0;
         lv[j][0] = 0;
     }
-    // level 0: one root entry per job (no end phase: far fewer items than waves)
+    // level 0: one root entry per job
     const uint32_t njobs = nctx * njobs_per_ctx;
     uint32_t job_live[kMaxJobs];
     for (uint32_t k = 0; k < kMaxJobs; k++) job_live[k] = 1;
     ItemLayout lay;
-    item_layout(job_live, njobs, unit, max_group, grid_waves, false, lay, max_wpi);
-    for (uint32_t k = 0; k < njobs; k++) {
-        ctl->item_begin[k] = lay.begin_a[k];
-        ctl->item_begin_b[k] = lay.begin_b[k];
-        ctl->split[k] = lay.split[k];
-    }
+    item_layout(job_live, njobs, unit, max_group, grid_waves, lay, max_wpi);
+    for (uint32_t k = 0; k < njobs; k++) ctl->item_begin[k] = lay.begin[k];
     ctl->group = lay.g;
-    ctl->group_b = lay.g_b;
     ctl->wpi = lay.wpi;
-    ctl->items_a = lay.items_a;
     ctl->total_items = lay.total;
 }
 

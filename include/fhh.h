@@ -747,10 +747,10 @@ int fhh_set_expand_grid(fhh_ctx* ctx, int blocks);
 /* Test / diagnostic ABI, pure host arithmetic (no GPU): the work decomposition k_expand variant
  * `variant` gets on a grid of grid_blocks workgroups for a launch of njobs (<= 8) jobs with n_live[k]
  * live entries each over nw 64-client words — the same function the host launches and the device loop's
- * kernels call. g = entries per item, wpi = words per item, items_a = bulk items, total = all items
+ * kernels call. g = entries per item, wpi = words per item, total = the launch's items
  * (any output may be NULL). FHH_E_ARG for a variant not in this build or empty shapes. */
 int fhh_expand_layout(int variant, int grid_blocks, uint32_t njobs, const uint32_t* n_live, uint32_t nw, uint32_t* g,
-                      uint32_t* wpi, uint64_t* items_a, uint64_t* total);
+                      uint32_t* wpi, uint64_t* total);
 int fhh_reset_stats(fhh_ctx* ctx);
 /* 1 to time every k_expand launch with HIP events (default 1); K > 1 times every K-th launch
  * of the device level loop (a pair of event records costs the stream a few microseconds). */
@@ -773,11 +773,6 @@ int fhh_microbench_hybrid(int device, int nb, double* rates);
  * 1 x 1024 (expand -> prune); 3 -> 1 x 1024; 4 / 5 -> alternating a 64 MiB writer (normal /
  * nontemporal stores) with 1 x 1024; 6 / 7 -> as 2 / 4 captured in a hipGraph and replayed. */
 int fhh_debug_launch_gaps(int device, int which, int reps, double* us_per_kernel);
-/* Wave timeline of the profiling k_expand variant 36 (tools/tail_profile.py): arm with a device
- * buffer of cap launches x grid waves x 3 u64 ({start after the LDS table fill, exit, items},
- * 100 MHz s_memrealtime ticks; buf NULL disarms); launches = launches recorded so far. */
-int fhh_wave_profile_arm(int device, uint64_t* buf, uint32_t cap);
-int fhh_wave_profile_launches(int device, uint32_t* launches);
 
 /* Device-to-device copy (synchronous): the channel stand-in of the in-process two-party runs,
  * which move each party's messages into buffers the other party owns. */

@@ -227,12 +227,9 @@ int main() {
         fhh::prg_ctrl_bits(c2[0], 1, bit, ybit);
         if (bit != 1 || ybit != 1) fails++;
     }
-    fails += check_layout<fhh::TabT0R64<HostOps>>(rng, ref_aes0);
     fails += check_layout<fhh::Tab4T32<HostOps>>(rng, ref_aes0);
     fails += check_layout<fhh::TabT0R32<HostOps>>(rng, ref_aes0);
-    fails += check_layout<fhh::TabT01R32<HostOps>>(rng, ref_aes0);
     fails += check_pair<fhh::Tab4T32<HostOps>>(rng);
-    fails += check_pair<fhh::TabT0R64<HostOps>>(rng);
     fails += check_pair_medium<fhh::Tab4T32<HostOps>>(rng);
     if (fails) { std::printf("FAIL %d\n", fails); return 1; }
     std::printf("OK\n");

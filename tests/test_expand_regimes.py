@@ -93,8 +93,7 @@ def frontier_shapes(d: int):
 # ---- item_layout, restated -------------------------------------------------------------------------
 
 def layout_port(n_live, nw, grid_waves, max_group, max_wpi):
-    """csrc/fhh_internal.h item_layout without the end phase (no built variant lays one out):
-    (g, wpi, items_a, total)."""
+    """csrc/fhh_internal.h item_layout: (g, wpi, total)."""
     entries = sum(n_live)
     g = min(max(entries * nw // (2 * grid_waves), 1), max_group)
     groups = sum((x + g - 1) // g for x in n_live)
@@ -105,17 +104,17 @@ def layout_port(n_live, nw, grid_waves, max_group, max_wpi):
         while wpi > 1 and groups * ((nw + wpi - 1) // wpi) < MW_ITEMS_PER_WAVE * grid_waves:
             wpi -= 1
     total = ((nw + wpi - 1) // wpi) * groups
-    return g, wpi, total, total
+    return g, wpi, total
 
 
 def lib_layout(lib, variant, grid, n_live, nw):
     nl = (ctypes.c_uint32 * len(n_live))(*n_live)
     g, wpi = ctypes.c_uint32(), ctypes.c_uint32()
-    ia, tot = ctypes.c_uint64(), ctypes.c_uint64()
+    tot = ctypes.c_uint64()
     rc = lib.fhh_expand_layout(variant, grid, len(n_live), nl, nw, ctypes.byref(g), ctypes.byref(wpi),
-                               ctypes.byref(ia), ctypes.byref(tot))
+                               ctypes.byref(tot))
     assert rc == 0, lib.fhh_last_error(None)
-    return g.value, wpi.value, ia.value, tot.value
+    return g.value, wpi.value, tot.value
 
 
 def launch_plan(case):
@@ -167,8 +166,8 @@ def test_expand_layout_rejects_bad_arguments(fhh):
     for variant, grid, njobs, nl, nw in [(0, 1, 1, one, 1), (53, 1, 1, one, 1), (-1, 1, 1, one, 1), (52, 0, 1, one, 1),
                                          (52, 1, 0, one, 1), (52, 1, 9, one, 1), (52, 1, 1, None, 1),
                                          (52, 1, 1, one, 0)]:
-        assert lib.fhh_expand_layout(variant, grid, njobs, nl, nw, None, None, None, None) != 0
-    assert lib.fhh_expand_layout(52, 1, 1, one, 1, None, None, None, None) == 0
+        assert lib.fhh_expand_layout(variant, grid, njobs, nl, nw, None, None, None) != 0
+    assert lib.fhh_expand_layout(52, 1, 1, one, 1, None, None, None) == 0
 
 
 def test_cases_visit_every_regime(fhh):
@@ -182,7 +181,7 @@ def test_cases_visit_every_regime(fhh):
         nw, nwaves = (n + 63) // 64, grid * WAVES_PER_BLOCK
         prev_wpi = None
         for n_live in launch_plan(case):
-            g, wpi, _, total = lib_layout(lib, variant, grid, n_live, nw)
+            g, wpi, total = lib_layout(lib, variant, grid, n_live, nw)
             seen_g.add(g)
             partial_group |= g > 1 and any(x % g for x in n_live)
             seen_static.add(total <= nwaves)

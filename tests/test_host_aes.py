@@ -31,7 +31,7 @@ def test_transpose32_host(tmp_path):
 
 
 def test_item_layout_host(tmp_path):
-    """k_expand's two-phase work decomposition covers every (job, entry, word) exactly once."""
+    """k_expand's work decomposition and item decode cover every (job, entry, word) exactly once."""
     if not shutil.which("hipcc"):
         pytest.skip("hipcc not available")
     exe = tmp_path / "item_layout"

@@ -1,6 +1,6 @@
 """Register budget of the hot kernel (CPU, hipcc cross-compile): the default k_expand variant
-(kDefaultVariant = 52 in csrc/fhh_host.cpp = X(52, Tab4T32, NB 4, 1024 threads, MINW 1,
-dynamic, FLAGS 6 | 4096 | 8192) in csrc/fhh_kernels.hip) must not spill and must keep 4 waves per SIMD.
+(kDefaultVariant = 52 in csrc/fhh_host.cpp = X(52, PAIR, MW, NTL all true, ...) in
+csrc/fhh_kernels.hip, 1024 threads) must not spill and must keep 4 waves per SIMD.
 A spill once crept in through extra item-decode state and cost 4-8 %."""
 import os
 import re
@@ -10,7 +10,7 @@ import subprocess
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DEFAULT_EXPAND = "_ZN3fhh8k_expandINS_7Tab4T32INS_7DevOpsXEEELi4ELi1024ELi1ELb0ELi12294EEEvNS_12ExpandLaunchEPj"
+DEFAULT_EXPAND = "_ZN3fhh8k_expandILb1ELb1ELb1EEEvNS_12ExpandLaunchEPj"
 
 
 def _resource_usage(src, tmp_path):
