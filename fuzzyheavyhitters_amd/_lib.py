@@ -38,7 +38,7 @@ EXPORTS = [
     "fhh_add_keys", "fhh_add_keys_bincode", "fhh_gen_keys_pair", "fhh_num_clients", "fhh_export_keys",
     "fhh_tree_init", "fhh_tree_crawl", "fhh_tree_crawl_last", "fhh_node_sums_fe",
     "fhh_node_sums_fe255", "fhh_tree_prune", "fhh_tree_prune_last", "fhh_frontier_size",
-    "fhh_final_shares", "fhh_export_states", "fhh_keep_values", "fhh_keep_values_last",
+    "fhh_final_shares", "fhh_export_states", "fhh_keep_values", "fhh_keep_values_last", "fhh_keep_values_ring32",
     "fhh_final_values", "fhh_sim_eq_count", "fhh_sim_ot_sums", "fhh_sim_crawl",
     "fhh_get_stats", "fhh_reset_stats", "fhh_set_timing", "fhh_device_info", "fhh_microbench", "fhh_microbench_gather", "fhh_microbench_hybrid", "fhh_sketch_set_impl", "fhh_sketch_plan",
     "fhh_debug_launch_gaps",
@@ -196,7 +196,7 @@ class FhhGbCfg(ctypes.Structure):
     """fhh_gb_cfg: the garbler's (server 0's) own material for one chunk (include/fhh.h)."""
     _fields_ = [
         ("mask", ctypes.c_uint32),
-        ("form", ctypes.c_uint32),   # FE levels: 0 garbled table (2d <= 4), 1 half-gates circuit
+        ("form", ctypes.c_uint32),   # FE levels: 0 garbled table (2d <= 4), 1 half-gates circuit, 2 table in Z_2^32
         ("base_chosen", ctypes.c_uint8 * (2 * 128 * 16)),
         ("base_choice", ctypes.c_uint8 * (2 * 16)),
         ("child_begin", ctypes.c_uint64),
@@ -325,6 +325,7 @@ def lib():
         "fhh_export_states": (i, [vp, u64p, u8p, u8p, u8p]),
         "fhh_keep_values": (i, [u64, u64p, u64p, u64, u8p]),
         "fhh_keep_values_last": (i, [u32, u32p, u32p, u64, u8p]),
+        "fhh_keep_values_ring32": (i, [u64, u64p, u64p, u64, u8p]),
         "fhh_final_values": (i, [u32p, u32p, u64, u32p]),
         "fhh_sim_eq_count": (i, [vp, vp, u64p]),
         "fhh_sim_ot_sums": (i, [vp, vp, u64, vp, vp]),

@@ -266,6 +266,21 @@ class KeyCollection:
         return keep.astype(bool)
 
     @staticmethod
+    def keep_values_ring32(nclients: int, threshold: int, vals0, vals1):
+        """keep_values on the servers' Z_2^32 sums (two_party_crawl form "table32"): keep iff
+        (v0 - v1) mod 2^32 >= threshold. The client total must be below 2^32 (the count is then the same
+        integer as in FE); a threshold or value of 2^32 or more is refused (FE sums fed in by mistake)."""
+        if nclients >= 1 << 32:
+            raise FhhError("keep_values_ring32: the client total must be below 2^32")
+        v0 = np.ascontiguousarray(np.asarray(vals0, np.uint64))
+        v1 = np.ascontiguousarray(np.asarray(vals1, np.uint64))
+        if v0.shape != v1.shape:
+            raise FhhError("keep_values_ring32: vals0.len() != vals1.len()")
+        keep = np.zeros(v0.size, np.uint8)
+        check(lib().fhh_keep_values_ring32(threshold, ptr(v0, u64p), ptr(v1, u64p), v0.size, ptr(keep)))
+        return keep.astype(bool)
+
+    @staticmethod
     def keep_values_last(nclients: int, threshold: int, vals0, vals1):
         if len(vals0) != len(vals1):
             raise FhhError("keep_values_last: vals0.len() != vals1.len() (collect.rs:967)")

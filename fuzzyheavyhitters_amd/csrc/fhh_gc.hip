@@ -606,6 +606,175 @@ __global__ __launch_bounds__(kGcThreads) void k_gt_eval(GcArgs a) {
     }
 }
 
+// ---- the row-major table over Z_2^32 (GcArgs::ring32 without lab_tm: b = 3, 4, the d = 2 tests) ----
+// k_gt_garble / k_gt_eval with the shares in Z_2^32 (oracle orc_gt_garble_ring32 / orc_gt_eval_ring32,
+// the arithmetic of k_gt_garble_tm's RING branch): row keys, tweak, colours and rstar as there; row 0's
+// value is lo32(H(K_0)), the pair (v, v +- 1 mod 2^32), rows 1 .. 2^b - 1 send lo32(H(K_r)) ^ pair[o_r] as
+// u32, SoA [2^b - 1][n]; the node values are u32 too (sh_gb / sh_ev read as uint32_t [n]). A row starts
+// at byte 4 r n and n may be odd, so every message and value moves by a 4-B access. Kernels of their own:
+// the FE instantiations above keep their code and register budgets.
+template <int B>
+__global__ __launch_bounds__(kGcThreads) void k_gt_garble_r32(GcArgs a) {
+    __shared__ uint32_t tbl_gc[GcTab::kWords];
+    if ((uint64_t)blockIdx.x * kGcThreads >= gc_active(a)) return;   // no tests: skip the table fill
+    gc_fill(tbl_gc);
+    uint32_t b0, b1;
+    GcTab::bases(threadIdx.x & 63, b0, b1);
+    constexpr uint32_t R = 1u << B;
+    constexpr int NB = R < 4 ? (int)R : 4;   // rows per AES pass
+    const uint64_t n = a.G * a.N;
+    const uint64_t Npad = (uint64_t)a.nw * 64;
+    uint32_t* msgs = reinterpret_cast<uint32_t*>(a.gt_msgs);
+    uint32_t* vals = reinterpret_cast<uint32_t*>(a.sh_gb);
+    uint32_t Dk[B][4];   // sigma^k(Delta)
+#pragma unroll
+    for (int c = 0; c < 4; c++) Dk[0][c] = a.delta[c];
+#pragma unroll
+    for (int k = 1; k < B; k++) {
+#pragma unroll
+        for (int c = 0; c < 4; c++) Dk[k][c] = Dk[k - 1][c];
+        gf_dbl(Dk[k]);
+    }
+    const uint64_t n_act = gc_active(a);
+    const uint64_t stride = (uint64_t)gridDim.x * kGcThreads;
+    for (uint64_t t = (uint64_t)blockIdx.x * kGcThreads + threadIdx.x; t < n_act; t += stride) {
+        const uint64_t g = t / a.N;
+        const uint32_t i = (uint32_t)(t - g * a.N);
+        const uint64_t tw = a.gate_base + a.g_off * a.N + t;   // the test's index in the whole level
+        uint32_t S[4] = {0u, 0u, 0u, 0u}, col = 0;
+#pragma unroll
+        for (int k = B - 1; k >= 0; k--) {   // Horner: S = sigma(S) ^ Z_k
+            uint32_t z[4];
+            ld_blk(a.ev_labels, g * B + k, Npad, i, z);   // E_k, the labels OT's q
+            const uint32_t xb = plane_bit(a.gb_planes, a.g_off + g, B, k, a.nw, i);
+            gf_dbl(S);
+#pragma unroll
+            for (int c = 0; c < 4; c++) {
+                z[c] ^= xb ? 0u : a.delta[c];   // Z_k = E_k ^ (x_k ? 0 : Delta)
+                S[c] ^= z[c];
+            }
+            col |= (z[0] & 1u) << k;
+        }
+        S[0] ^= (uint32_t)tw;
+        S[1] ^= (uint32_t)(tw >> 32);
+        const uint32_t rstar = ~col & (R - 1);   // the row whose z are all 1 (eq = 1)
+        uint32_t p0 = 0, p1 = 0;
+#pragma unroll
+        for (uint32_t pass = 0; pass < R / NB; pass++) {
+            uint32_t h[NB][4];
+#pragma unroll
+            for (int j = 0; j < NB; j++) {
+                const uint32_t flip = (pass * NB + j) ^ col;   // z_k of the row = bit k of r ^ col
+#pragma unroll
+                for (int c = 0; c < 4; c++) {
+                    uint32_t w = S[c];
+#pragma unroll
+                    for (int k = 0; k < B; k++) w ^= ((flip >> k) & 1u) ? Dk[k][c] : 0u;
+                    h[j][c] = w;
+                }
+            }
+            aes0_mmo_tab<DevOpsX, GcTab, NB>(h, tbl_gc, b0, b1);   // cr_hash: pi(K) ^ K
+#pragma unroll
+            for (int j = 0; j < NB; j++) {
+                const uint32_t r = pass * NB + j;
+                const uint32_t o = (uint32_t)(r == rstar) ^ a.mask;
+                if (r == 0) {   // row 0's value pair[o_0] is lo32(H(K_0)): it fixes v
+                    const uint32_t h32 = h[0][0];
+                    const uint32_t v = o == 0 ? h32 : (a.mask ? h32 - 1u : h32 + 1u);
+                    p0 = v;
+                    p1 = a.mask ? v + 1u : v - 1u;
+                    vals[t] = a.mask ? v + 1u : v;   // r1 = v + mask
+                } else {
+                    msgs[(uint64_t)(r - 1) * n + t] = h[j][0] ^ (o ? p1 : p0);
+                }
+            }
+        }
+    }
+}
+
+template <int B>
+__global__ __launch_bounds__(kGcThreads) void k_gt_eval_r32(GcArgs a) {
+    __shared__ uint32_t tbl_gc[GcTab::kWords];
+    if ((uint64_t)blockIdx.x * kGcThreads >= gc_active(a)) return;
+    gc_fill(tbl_gc);
+    uint32_t b0, b1;
+    GcTab::bases(threadIdx.x & 63, b0, b1);
+    const uint64_t n = a.G * a.N;
+    const uint64_t Npad = (uint64_t)a.nw * 64;
+    const uint64_t n_act = gc_active(a);
+    const uint32_t* msgs = reinterpret_cast<const uint32_t*>(a.gt_msgs);
+    uint32_t* vals = reinterpret_cast<uint32_t*>(a.sh_ev);
+    constexpr int U = FHH_GT_EVAL_U;   // tests per lane per pass (U AES blocks in flight)
+    const uint64_t stride = (uint64_t)gridDim.x * kGcThreads;
+    for (uint64_t t0 = (uint64_t)blockIdx.x * kGcThreads + threadIdx.x; t0 < n_act; t0 += U * stride) {
+        uint32_t h[U][4], row[U];
+        uint64_t tt[U];
+#pragma unroll
+        for (int u = 0; u < U; u++) {
+            const uint64_t t = t0 + u * stride;
+            tt[u] = t;
+            const uint64_t tc = t < n_act ? t : t0;   // a valid test for the padding block
+            const uint64_t g = tc / a.N;
+            const uint32_t i = (uint32_t)(tc - g * a.N);
+            const uint64_t tw = a.gate_base + a.g_off * a.N + tc;
+            uint32_t S[4] = {0u, 0u, 0u, 0u}, r = 0;
+#pragma unroll
+            for (int k = B - 1; k >= 0; k--) {
+                uint32_t z[4];
+                ld_blk(a.ev_labels, g * B + k, Npad, i, z);   // t_k, z_k's active label
+                gf_dbl(S);
+#pragma unroll
+                for (int c = 0; c < 4; c++) S[c] ^= z[c];
+                r |= (z[0] & 1u) << k;
+            }
+            S[0] ^= (uint32_t)tw;
+            S[1] ^= (uint32_t)(tw >> 32);
+#pragma unroll
+            for (int c = 0; c < 4; c++) h[u][c] = S[c];
+            row[u] = r;
+        }
+        aes0_mmo_tab<DevOpsX, GcTab, U>(h, tbl_gc, b0, b1);
+#pragma unroll
+        for (int u = 0; u < U; u++) {
+            const uint64_t t = tt[u];
+            if (t >= n_act) continue;
+            vals[t] = row[u] ? (h[u][0] ^ msgs[(uint64_t)(row[u] - 1) * n + t]) : h[u][0];
+        }
+    }
+}
+
+// Per-child sums of the u32 node values [C][n] of the kernels above: workgroup (x, c) adds its slice of
+// child c's row, at most kRingSumSlice values, in u64 and adds the wave sums to sums[c] (zeroed by the
+// caller) with one atomic per wave. The u64 totals cannot wrap (n < 2^32 values below 2^32) and integer
+// addition commutes, so the host's single reduction mod 2^32 does not depend on the order of the adds.
+constexpr int kRingSumThreads = 256;
+constexpr uint32_t kRingSumSlice = 4096;
+__global__ __launch_bounds__(kRingSumThreads) void k_ring32_child_sums(const uint32_t* vals, uint64_t n, uint64_t* sums) {
+    const uint64_t c = blockIdx.y;
+    const uint64_t lo = (uint64_t)blockIdx.x * kRingSumSlice;
+    const uint64_t hi = lo + kRingSumSlice < n ? lo + kRingSumSlice : n;
+    const uint32_t* row = vals + c * n;
+    uint64_t acc = 0;
+    for (uint64_t i = lo + threadIdx.x; i < hi; i += kRingSumThreads) acc += row[i];
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off, 64);
+    if ((threadIdx.x & 63) == 0 && acc) atomicAdd(reinterpret_cast<unsigned long long*>(sums + c), (unsigned long long)acc);
+}
+
+hipError_t launch_ring32_child_sums(const uint32_t* vals, uint64_t n, uint64_t C, uint64_t* sums, hipStream_t stream) {
+    if (n == 0 || C == 0) return hipSuccess;
+    if (!vals || !sums) return hipErrorInvalidValue;
+    const uint64_t per = (n + kRingSumSlice - 1) / kRingSumSlice;
+    for (uint64_t c0 = 0; c0 < C; c0 += 65535) {   // grid.y holds 65535 children per launch
+        const uint64_t cc = C - c0 < 65535 ? C - c0 : 65535;
+        hipLaunchKernelGGL(k_ring32_child_sums, dim3((uint32_t)per, (uint32_t)cc), dim3(kRingSumThreads), 0, stream,
+                           vals + c0 * n, n, sums + c0);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
 // ---- r06: the garbled table on the labels OT's tile-major matrices ------------------------------
 // k_gt_garble / k_gt_eval read one row-major 16-B label per (test, bit), which k_ot_rows_out produced
 // from the tile-major Q / T the OT expands write: 32 B of HBM per OT and party (read + write) and a
@@ -958,6 +1127,11 @@ static hipError_t gt_launch(const GcArgs& a, bool garble, hipStream_t stream) {
     }
     const uint64_t need = (n + kGcThreads - 1) / kGcThreads;
     const int grid = (int)(need < (uint64_t)cus * 8 ? (need ? need : 1) : (uint64_t)cus * 8);
+    if constexpr (B > kGtTmMaxBits) if (a.ring32) {   // Z_2^32 shares on the row-major labels (b = 3, 4)
+        if (garble) hipLaunchKernelGGL(k_gt_garble_r32<B>, dim3(grid), dim3(kGcThreads), 0, stream, a);
+        else hipLaunchKernelGGL(k_gt_eval_r32<B>, dim3(grid), dim3(kGcThreads), 0, stream, a);
+        return hipGetLastError();
+    }
     if (garble) hipLaunchKernelGGL(k_gt_garble<B>, dim3(grid), dim3(kGcThreads), 0, stream, a);
     else hipLaunchKernelGGL(k_gt_eval<B>, dim3(grid), dim3(kGcThreads), 0, stream, a);
     return hipGetLastError();
@@ -969,7 +1143,8 @@ static hipError_t gt_dispatch(const GcArgs& a, bool garble, hipStream_t stream) 
         return hipErrorInvalidValue;
     // r06 tile-major labels: 512-test tiles per group, b <= 2 (gt_tm_bits)
     if (a.lab_tm && (a.nw % 8 != 0 || a.bits > (uint32_t)kGtTmMaxBits)) return hipErrorInvalidValue;
-    if (a.ring32 && !a.lab_tm) return hipErrorInvalidValue;   // Z_2^32: the tile-major kernels only
+    // Z_2^32: the tile-major kernels at b <= 2, k_gt_garble_r32 / k_gt_eval_r32 on row-major labels at b = 3, 4
+    if (a.ring32 && !a.lab_tm && a.bits <= (uint32_t)kGtTmMaxBits) return hipErrorInvalidValue;
     switch (a.bits) {
         case 1: return gt_launch<1>(a, garble, stream);
         case 2: return gt_launch<2>(a, garble, stream);

@@ -565,16 +565,16 @@ static int gt_cot_host(fhh_ctx* ctx, uint64_t n, uint32_t bits, const uint8_t* g
     int rc = ctx_set_device(ctx);
     if (rc) return rc;
     if (bits < 1 || bits > (uint32_t)kGtMaxBits) return ctx->fail(FHH_E_ARG, "gt_cot: bits must be in [1, 4]");
-    if (ring32 && bits > (uint32_t)kGtTmMaxBits)
-        return ctx->fail(FHH_E_ARG, "gt_cot: the Z_2^32 table runs on the tile-major kernels (bits <= 2)");
     if (n == 0) return FHH_OK;
     if (!gb_bits || !ev_bits || !base_seeds || !base_choice || !gb_share || !ev_share)
         return ctx->fail(FHH_E_ARG, "gt_cot: NULL argument");
     if (!(base_choice[0] & 1)) return ctx->fail(FHH_E_ARG, "gt_cot: s is the free-XOR Delta: its bit 0 must be 1");
     if (n > 0xFFFFFFFFull) return ctx->fail(FHH_E_ARG, "gt_cot: n must fit 32 bits");
     // r06: b <= 2 runs the tile-major table kernels on Q / T (the level loop's form), whose OT index wants
-    // plane rows of whole 512-client tiles; b = 3, 4 the row-major labels of k_ot_rows_out
+    // plane rows of whole 512-client tiles; b = 3, 4 the row-major labels of k_ot_rows_out (Z_2^32 there:
+    // k_gt_garble_r32 / k_gt_eval_r32, whose node values are u32)
     const bool tm = bits <= (uint32_t)kGtTmMaxBits;
+    const bool val32 = ring32 && !tm;
     const uint64_t nw = tm ? (n + 511) / 512 * 8 : (n + 63) / 64, npad = 64 * nw, m = (uint64_t)bits * npad;
     const uint64_t R = 1ull << bits;
     std::vector<uint64_t> planes[2];
@@ -640,8 +640,17 @@ static int gt_cot_host(fhh_ctx* ctx, uint64_t n, uint32_t bits, const uint8_t* g
     }
     rc = ctx_sync(ctx);
     if (rc) return rc;
-    HIP_TRY(ctx, hipMemcpy(gb_share, dsh.p, n * 8, hipMemcpyDeviceToHost));
-    HIP_TRY(ctx, hipMemcpy(ev_share, dsh.as<uint64_t>() + n, n * 8, hipMemcpyDeviceToHost));
+    if (val32) {   // u32 values [n] at dsh and at dsh + n u64 (the kernels' sh_gb / sh_ev), zero-extended
+        std::vector<uint32_t> h(n);
+        uint64_t* dst[2] = {gb_share, ev_share};
+        for (int w = 0; w < 2; w++) {
+            HIP_TRY(ctx, hipMemcpy(h.data(), dsh.as<uint64_t>() + w * n, n * 4, hipMemcpyDeviceToHost));
+            for (uint64_t t = 0; t < n; t++) dst[w][t] = h[t];
+        }
+    } else {
+        HIP_TRY(ctx, hipMemcpy(gb_share, dsh.p, n * 8, hipMemcpyDeviceToHost));
+        HIP_TRY(ctx, hipMemcpy(ev_share, dsh.as<uint64_t>() + n, n * 8, hipMemcpyDeviceToHost));
+    }
     if (msgs && R > 1 && ring32) {   // SoA [R-1][n] u32 on the device -> [n][R-1] (zero-extended)
         std::vector<uint32_t> h((R - 1) * n);
         HIP_TRY(ctx, hipMemcpy(h.data(), dm.p, h.size() * 4, hipMemcpyDeviceToHost));
@@ -715,6 +724,7 @@ struct PartyState {
     bool last = false;          // tree_crawl_last: FieldElm shares (BlockPair = 2 OTs per test)
     bool lshare = false;        // r05c (FE levels): the share from the GC output labels, no OT 2
     bool ltable = false;        // r05d (FE levels, bits <= kGtMaxBits): one garbled table per test
+    bool lring = false;         // form 2 (ltable): the table's shares, messages and node values in Z_2^32 (u32)
     bool ltm = false;           // r06 (ltable, bits <= kGtTmMaxBits): the table kernels read the labels OT's
                                 // tile-major Q / T (no row transposes); npad / nw = whole 512-client tiles
     // C = this instance's children: the chunk [c_off, c_off + C) of the level's level_C children
@@ -738,7 +748,8 @@ struct PartyState {
     DevBuf T, U, Q, Y;          // OT matrices (T / Q private) and messages (U or y)
     DevBuf choices2;            // evaluator: the GC outputs packed as OT 2's choice words
     DevBuf out;                 // evaluator: GC output bytes (eq ^ mask)
-    DevBuf vals;                // the level's node values [level_C][n] (u64, or a BlockPair at the last level)
+    DevBuf vals;                // the level's node values [level_C][n] (u64, u32 with lring, or a BlockPair at the last level)
+    DevBuf ring_sums;           // lring without lfused: the per-child u64 totals of vals (k_ring32_child_sums)
     std::vector<uint32_t> rk_host;
     uint64_t bytes_sent = 0;    // this ctx's outgoing message bytes for the level
     uint32_t ss_k = 1;          // r06: 1 IKNP, 2 / 4 SoftSpoken (both OT kinds; fhh_ev_cfg / fhh_gb_cfg.ot_ss_k)
@@ -771,6 +782,10 @@ int party_begin(fhh_ctx* ctx, int role, uint64_t child_begin, uint64_t child_cou
     if (ctx->phase != Phase::kPending && ctx->phase != Phase::kPendingLast)
         return ctx->fail(FHH_E_STATE, "party: needs a pending tree_crawl / tree_crawl_last");
     if (2 * ctx->d > (uint32_t)kGcMaxBits) return ctx->fail(FHH_E_ARG, "party: d <= 4");
+    // the Z_2^32 shares exist for the table only: running the circuit instead would hand the leader FE sums
+    if (form == 2 && 2 * ctx->d > (uint32_t)kGtMaxBits)
+        return ctx->fail(FHH_E_ARG, "party: form 2 (the garbled table with Z_2^32 shares) needs 2d <= 4; there is no "
+                                    "ring form of the circuit");
     PartyState& P = party_of(ctx);
     const bool last = ctx->phase == Phase::kPendingLast;
     // the chunk of children (collect.rs:423-430: a level's tests split over channels), in order
@@ -804,7 +819,8 @@ int party_begin(fhh_ctx* ctx, int role, uint64_t child_begin, uint64_t child_cou
     P.tests = P.C * P.n;
     P.per2 = P.last ? 2 : 1;
     P.lshare = !P.last;
-    P.ltable = P.lshare && P.bits <= (uint32_t)kGtMaxBits && form == 0;   // form 1: the circuit (r05c)
+    P.ltable = P.lshare && P.bits <= (uint32_t)kGtMaxBits && form != 1;   // form 1: the circuit (r05c)
+    P.lring = P.ltable && form == 2;   // form 2: the table over Z_2^32 (the FieldElm level is form 0's)
     P.ltm = P.ltable && P.bits <= (uint32_t)kGtTmMaxBits;
     if (P.ltm) {   // plane rows and the OT index over whole 512-client tiles (both parties alike: n is public)
         P.nw = (ctx->nw + 7) / 8 * 8;
@@ -833,7 +849,7 @@ int party_begin(fhh_ctx* ctx, int role, uint64_t child_begin, uint64_t child_cou
         HIP_TRY(ctx, hipMemsetAsync(P.partials.p, 0, std::max<uint64_t>(LC, 1) * 4 * 8, ctx->stream));
         P.partials_host.assign(std::max<uint64_t>(LC, 1) * 4, 0);
     } else if (b == 0) {
-        HIP_TRY(ctx, P.vals.ensure(std::max<uint64_t>(LC * P.n * P.per2, 1) * (P.last ? 16 : 8)));
+        HIP_TRY(ctx, P.vals.ensure(std::max<uint64_t>(LC * P.n * P.per2, 1) * (P.last ? 16 : P.lring ? 4 : 8)));
     }
     return FHH_OK;
 }
@@ -917,7 +933,7 @@ int party_ot_buffers(fhh_ctx* ctx, PartyState& P, uint64_t m, bool receiver, boo
 }
 
 uint64_t gc_bytes(const PartyState& P) {
-    if (P.ltable) return P.tests * (((uint64_t)1 << P.bits) - 1) * 8;   // rows 1 .. 2^bits - 1, 8 B each
+    if (P.ltable) return P.tests * (((uint64_t)1 << P.bits) - 1) * (P.lring ? 4 : 8);   // rows 1 .. 2^bits - 1, 8 B (Z_2^32: 4 B) each
     return P.tests * ((uint64_t)2 * (P.bits - 1) * 16 + 1 + (P.lshare ? 8 : 0));
 }
 uint64_t y2_bytes(const PartyState& P) { return P.m2 * (P.last ? 16 : 8); }
@@ -938,7 +954,7 @@ void gc_layout(const PartyState& P, uint8_t* base, GcArgs& g) {
     g.gb_labels = nullptr;
     g.sh_y = P.lshare ? reinterpret_cast<uint64_t*>(base + tb) : nullptr;
     g.decode = base + tb + (P.lshare ? 8 * t : 0);
-    if (P.ltable) {   // r05d: the gc message is the garbled table's rows 1 .. 2^bits - 1 (SoA, u64)
+    if (P.ltable) {   // r05d: the gc message is the garbled table's rows 1 .. 2^bits - 1 (SoA, u64; lring: u32)
         g.tables = nullptr;
         g.sh_y = nullptr;
         g.decode = nullptr;
@@ -946,8 +962,33 @@ void gc_layout(const PartyState& P, uint8_t* base, GcArgs& g) {
     }
 }
 
-// this chunk's rows of the level's node values (u64 FE, or a BlockPair at the last level)
-uint8_t* party_vals(PartyState& P) { return P.vals.as<uint8_t>() + P.c_off * P.n * P.per2 * (P.last ? 16 : 8); }
+// this chunk's rows of the level's node values (u64 FE, u32 in Z_2^32, or a BlockPair at the last level)
+uint8_t* party_vals(PartyState& P) {
+    return P.vals.as<uint8_t>() + P.c_off * P.n * P.per2 * (P.last ? 16 : P.lring ? 4 : 8);
+}
+
+// form 2: this ctx's per-child totals of the level's Z_2^32 node values, added into acc [level_C] (u64; the
+// caller reduces mod 2^32 once): the fused partials' low sums (b <= 2), or k_ring32_child_sums over vals
+int party_ring_totals(fhh_ctx* ctx, PartyState& P, std::vector<uint64_t>& acc) {
+    const uint64_t LC = P.level_C;
+    if (P.lfused) {
+        const int k0 = P.role == 0 ? 0 : 2;
+        for (uint64_t c = 0; c < LC; c++) acc[c] += P.partials_host[4 * c + k0] + (P.partials_host[4 * c + k0 + 1] << 32);
+        return FHH_OK;
+    }
+    if (LC == 0) return FHH_OK;
+    int rc = ctx_set_device(ctx);
+    if (rc) return rc;
+    HIP_TRY(ctx, P.ring_sums.ensure(LC * 8));
+    HIP_TRY(ctx, hipMemsetAsync(P.ring_sums.p, 0, LC * 8, ctx->stream));
+    HIP_TRY(ctx, launch_ring32_child_sums(P.vals.as<uint32_t>(), P.n, LC, P.ring_sums.as<uint64_t>(), ctx->stream));
+    std::vector<uint64_t> h(LC);
+    HIP_TRY(ctx, hipMemcpyAsync(h.data(), P.ring_sums.p, LC * 8, hipMemcpyDeviceToHost, ctx->stream));
+    rc = ctx_sync(ctx);
+    if (rc) return rc;
+    for (uint64_t c = 0; c < LC; c++) acc[c] += h[c];
+    return FHH_OK;
+}
 
 // the chunk's gate tweaks: the level in bits 40+ (Delta = the labels session's s may serve several levels
 // when base OTs are reused), then the test's index in the whole level (c_off n + t)
@@ -962,7 +1003,8 @@ extern "C" {
 int fhh_ev_ot_labels(fhh_ctx* ctx, const fhh_ev_cfg* cfg, const uint8_t** u_dev, uint64_t* u_len) {
     CTX_CHECK(ctx);
     if (!cfg || !u_dev || !u_len) return ctx->fail(FHH_E_ARG, "ev_ot_labels: NULL argument");
-    if (cfg->form > 1) return ctx->fail(FHH_E_ARG, "ev_ot_labels: form must be 0 (table) or 1 (circuit)");
+    if (cfg->form > 2)
+        return ctx->fail(FHH_E_ARG, "ev_ot_labels: form must be 0 (table), 1 (circuit) or 2 (table, Z_2^32 shares)");
     if (cfg->ot_ss_k > 1 && cfg->ot_ss_k != 2 && cfg->ot_ss_k != 4)
         return ctx->fail(FHH_E_ARG, "ev_ot_labels: ot_ss_k must be 0 / 1 (IKNP), 2 or 4 (SoftSpoken)");
     int rc = party_begin(ctx, 1, cfg->child_begin, cfg->child_count, cfg->form);
@@ -1004,7 +1046,8 @@ int fhh_gb_ot_labels(fhh_ctx* ctx, const fhh_gb_cfg* cfg, const uint8_t* u_dev, 
                      uint64_t* y_len) {
     CTX_CHECK(ctx);
     if (!cfg || !y_dev || !y_len) return ctx->fail(FHH_E_ARG, "gb_ot_labels: NULL argument");
-    if (cfg->form > 1) return ctx->fail(FHH_E_ARG, "gb_ot_labels: form must be 0 (table) or 1 (circuit)");
+    if (cfg->form > 2)
+        return ctx->fail(FHH_E_ARG, "gb_ot_labels: form must be 0 (table), 1 (circuit) or 2 (table, Z_2^32 shares)");
     if (cfg->ot_ss_k > 1 && cfg->ot_ss_k != 2 && cfg->ot_ss_k != 4)
         return ctx->fail(FHH_E_ARG, "gb_ot_labels: ot_ss_k must be 0 / 1 (IKNP), 2 or 4 (SoftSpoken)");
     int rc = party_begin(ctx, 0, cfg->child_begin, cfg->child_count, cfg->form);
@@ -1053,6 +1096,7 @@ int fhh_gb_ot_labels(fhh_ctx* ctx, const fhh_gb_cfg* cfg, const uint8_t* u_dev, 
     gc_layout(P, P.gc.as<uint8_t>(), P.g);
     P.g.ev_ot = 1;
     P.g.lab_tm = P.ltm ? 1u : 0u;
+    P.g.ring32 = P.lring ? 1u : 0u;
     P.g.out = nullptr;
     // r05c: the garbler's node values r1 straight into the level's rows (the y it forms travels in gc);
     // r06 (ltm): added per child into the partials instead
@@ -1128,6 +1172,7 @@ int fhh_ev_evaluate(fhh_ctx* ctx, const uint8_t* gc_msg_dev, uint64_t gc_len, co
     gc_layout(P, const_cast<uint8_t*>(gc_msg_dev), g);
     g.ev_labels = P.ltm ? P.T.as<uint4>() : P.labels.as<uint4>();   // r06: the tile-major T itself
     g.lab_tm = P.ltm ? 1u : 0u;
+    g.ring32 = P.lring ? 1u : 0u;
     g.ev_ot = 1;
     g.out = P.out.as<uint8_t>();
     if (P.lfused) {   // r06: added per child into the partials
@@ -1232,7 +1277,8 @@ int fhh_party_node_sums(fhh_ctx* ctx, void* sums_a, void* sums_b) {
         if (rc) return rc;
         std::vector<const void*> v((size_t)S, nullptr);
         std::vector<PartyState*> fused_shards;
-        int last = -1, fused = -1;
+        std::vector<fhh_ctx*> ring_ctxs;
+        int last = -1, fused = -1, ring = -1;
         for (int k = 0; k < S; k++) {
             fhh_ctx* sh = nullptr;
             uint64_t nk = 0;
@@ -1250,10 +1296,27 @@ int fhh_party_node_sums(fhh_ctx* ctx, void* sums_a, void* sums_b) {
             // nothing valid in the buffer that path reads)
             if (fused >= 0 && fused != (int)P->lfused) return ctx->fail(FHH_E_STATE, "party_node_sums: shards disagree");
             fused = P->lfused;
+            // FE or Z_2^32 shares (forms 0 and 2 are both fused at d = 1: the sums' group must agree too)
+            if (ring >= 0 && ring != (int)P->lring) return ctx->fail(FHH_E_STATE, "party_node_sums: shards disagree");
+            ring = P->lring;
             v[(size_t)k] = P->vals.p;
             fused_shards.push_back(P);
+            ring_ctxs.push_back(sh);
         }
         if (last < 0) return ctx->fail(FHH_E_STATE, "party_node_sums: no shard holds clients");
+        if (ring == 1) {   // form 2: the shards' totals added, then reduced mod 2^32 once
+            const uint64_t LC = fused_shards[0]->level_C;
+            std::vector<uint64_t> acc(LC, 0);
+            for (size_t j = 0; j < fused_shards.size(); j++) {
+                if (fused_shards[j]->level_C != LC) return ctx->fail(FHH_E_STATE, "party_node_sums: shards disagree");
+                rc = party_ring_totals(ring_ctxs[j], *fused_shards[j], acc);
+                if (rc) return ctx->fail(rc, std::string("party_node_sums: ") + g_err);
+            }
+            uint64_t* sums = static_cast<uint64_t*>(sums_a);
+            if (sums)
+                for (uint64_t c = 0; c < LC; c++) sums[c] = acc[c] & 0xFFFFFFFFull;
+            return FHH_OK;
+        }
         if (fused == 1) {   // r06: the shards' host partials, summed
             const uint64_t LC = fused_shards[0]->level_C;
             std::vector<uint64_t> h(LC * 2, 0);
@@ -1277,6 +1340,15 @@ int fhh_party_node_sums(fhh_ctx* ctx, void* sums_a, void* sums_b) {
     if (!Pp || Pp->step != 3 || Pp->covered != Pp->level_C)
         return ctx->fail(FHH_E_STATE, "party_node_sums: the level's OTs are not finished for every child");
     PartyState& P = *Pp;
+    if (P.lring) {   // form 2: the party's sum mod 2^32, zero-extended
+        std::vector<uint64_t> acc(P.level_C, 0);
+        int rc = party_ring_totals(ctx, P, acc);
+        if (rc) return rc;
+        uint64_t* sums = static_cast<uint64_t*>(sums_a);
+        if (sums)
+            for (uint64_t c = 0; c < P.level_C; c++) sums[c] = acc[c] & 0xFFFFFFFFull;
+        return FHH_OK;
+    }
     if (P.lfused) {   // r06: the partials the garble / evaluate calls copied to the host
         const int k0 = P.role == 0 ? 0 : 2;
         uint64_t* sums = static_cast<uint64_t*>(sums_a);

@@ -2141,6 +2141,25 @@ int fhh_keep_values(uint64_t threshold, const uint64_t* vals0, const uint64_t* v
     return FHH_OK;
 }
 
+int fhh_keep_values_ring32(uint64_t threshold, const uint64_t* vals0, const uint64_t* vals1, uint64_t n, uint8_t* keep) {
+    if (n && (!vals0 || !vals1 || !keep)) {
+        g_err = "keep_values_ring32: NULL buffer";
+        return FHH_E_ARG;
+    }
+    if (threshold >> 32) {
+        g_err = "keep_values_ring32: the threshold must be below 2^32";
+        return FHH_E_ARG;
+    }
+    // checked before anything is written: a value of 2^32 or more is not a Z_2^32 sum (FE sums fed in by mistake)
+    for (uint64_t i = 0; i < n; i++)
+        if ((vals0[i] | vals1[i]) >> 32) {
+            g_err = "keep_values_ring32: value " + std::to_string(i) + " is not below 2^32 (FE sums? use fhh_keep_values)";
+            return FHH_E_ARG;
+        }
+    for (uint64_t i = 0; i < n; i++) keep[i] = (uint32_t)((uint32_t)vals0[i] - (uint32_t)vals1[i]) >= (uint32_t)threshold;
+    return FHH_OK;
+}
+
 int fhh_keep_values_last(uint32_t threshold, const uint32_t* vals0, const uint32_t* vals1, uint64_t n, uint8_t* keep) {
     if (n && (!vals0 || !vals1 || !keep)) {
         g_err = "keep_values_last: NULL buffer";

@@ -246,7 +246,8 @@ struct GcArgs {
     uint64_t* node_partials;
     uint64_t node_off;   // node_partials row of the launch's group 0 beyond g_off (the party ABI: its chunk's c_off)
     // r06 (lab_tm): 1 = the table's shares live in Z_2^32 instead of FE (row value lo32 of the
-    // hash, pair (v, v +- 1 mod 2^32), 4-B messages [2^b - 1][n] u32; the partials' low sums taken mod 2^32)
+    // hash, pair (v, v +- 1 mod 2^32), 4-B messages [2^b - 1][n] u32; the partials' low sums taken mod 2^32).
+    // Without lab_tm (bits = 3, 4: k_gt_garble_r32 / k_gt_eval_r32) sh_gb / sh_ev hold u32 values [G N] too
     uint32_t ring32;
 };
 constexpr int kGtMaxBits = 4;   // 16 rows (d = 2); wider tests keep the half-gates chain
@@ -411,6 +412,8 @@ hipError_t launch_gc_garble(const GcArgs& a, hipStream_t stream);
 hipError_t launch_gc_eval(const GcArgs& a, hipStream_t stream);
 hipError_t launch_gt_garble(const GcArgs& a, hipStream_t stream);   // r05d garbled table
 hipError_t launch_gt_eval(const GcArgs& a, hipStream_t stream);
+// sums[c] += the u32 node values vals [C][n] of child c, as u64 (sums zeroed by the caller; Z_2^32 table, b = 3, 4)
+hipError_t launch_ring32_child_sums(const uint32_t* vals, uint64_t n, uint64_t C, uint64_t* sums, hipStream_t stream);
 hipError_t launch_gather_hist(const uint32_t* sizes, uint32_t stride, const uint32_t* const* rows, uint32_t levels,
                               uint32_t* out, uint64_t cap, hipStream_t stream);
 // parity probe of the device loop (fhh_sim_config.probe_*): the pending children's states of a

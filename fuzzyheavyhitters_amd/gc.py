@@ -164,7 +164,7 @@ def table_cot(kc, gb_inputs, ev_inputs, mask: int, base_seeds, base_choice, gate
     """r05d, the FE levels' form (fhh_gt_cot_host, bits <= 4): the labels OT, then one garbled table
     of 2^bits rows for "the share of eq ^ mask" (Yao's garbled gate, point-and-permute) instead of the
     half-gates chain. Returns dict: msgs [n][2^bits - 1] u64, gb_share / ev_share [n] (gb - ev = eq mod
-    p), ev_zero / ev_active [n][bits][16]. ring32 (r06, bits <= 2; fhh_gt_cot_ring32_host): the shares in
+    p), ev_zero / ev_active [n][bits][16]. ring32 (r06, bits <= 4; fhh_gt_cot_ring32_host): the shares in
     Z_2^32 (4-B messages; gb - ev = eq mod 2^32), returned zero-extended in the same arrays."""
     g = np.ascontiguousarray(np.asarray(gb_inputs).astype(np.uint8) & 1)
     e = np.ascontiguousarray(np.asarray(ev_inputs).astype(np.uint8) & 1)

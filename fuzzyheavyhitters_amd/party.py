@@ -274,20 +274,27 @@ def two_party_crawl(c0: KeyCollection, c1: KeyCollection, threshold: float, ncli
     children (None: as many as `chunk_bytes` of both parties' buffers hold at ~512 B per test; 0: the
     whole level), one protocol instance per chunk. `level_log` (a list) receives one (level, children,
     crawl_s, gcot_s, node_sums_s) tuple per level. `form`: "table" (the FE levels' test as one garbled
-    table where 2d <= 4, r05d) or "circuit" (the half-gates circuit at every level, r05c) — a public
-    protocol choice both parties make alike. `ot_ss_k` (r06, public like form): 1 = IKNP OT extension, 2 / 4 =
+    table where 2d <= 4, r05d), "circuit" (the half-gates circuit at every level, r05c) or "table32" (the
+    table with its shares in Z_2^32: half the gc bytes at the FE levels, whose sums the leader thresholds with
+    keep_values_ring32 and whose recorded counts are (s0 - s1) mod 2^32; d <= 2 and a client total below 2^32
+    only, ValueError otherwise) — a public protocol choice both parties and the leader make alike. `ot_ss_k` (r06, public like form): 1 = IKNP OT extension, 2 / 4 =
     SoftSpoken with k = ot_ss_k (the U messages carry 128 / k rows + the GGM corrections)."""
     if ot_ss_k not in (1, 2, 4):
         raise ValueError(f"two_party_crawl: ot_ss_k {ot_ss_k!r}")
     if material not in ("fresh", "test"):
         raise ValueError(f"two_party_crawl: material {material!r}")
-    if form not in ("table", "circuit"):
+    if form not in ("table", "circuit", "table32"):
         raise ValueError(f"two_party_crawl: form {form!r}")
-    form_id = 0 if form == "table" else 1
+    form_id = {"table": 0, "circuit": 1, "table32": 2}[form]
+    ring32 = form_id == 2
     if base_ot_every not in ("level", "crawl"):
         raise ValueError(f"two_party_crawl: base_ot_every {base_ot_every!r}")
     L = levels or c0.depth
     n_total = nclients_total if nclients_total is not None else c0.num_clients()
+    if ring32 and c0.n_dims > 2:
+        raise ValueError(f"two_party_crawl: form 'table32' needs d <= 2 (no Z_2^32 form of the circuit), d = {c0.n_dims}")
+    if ring32 and n_total >= 1 << 32:
+        raise ValueError("two_party_crawl: form 'table32' needs a client total below 2^32")
     thr = max(1, int(threshold * n_total))
     thr_last = max(1, min(int(threshold * n_total), 0xFFFFFFFF))
     S = len(c0.shard_info()[0])
@@ -375,7 +382,7 @@ def two_party_crawl(c0: KeyCollection, c1: KeyCollection, threshold: float, ncli
             t3 = clock()
             res.level_children.append(C0)
             if not last:
-                keep = KeyCollection.keep_values(n_total, thr, s0, s1)
+                keep = (KeyCollection.keep_values_ring32 if ring32 else KeyCollection.keep_values)(n_total, thr, s0, s1)
                 t4 = clock()
                 c0.tree_prune(keep)
                 c1.tree_prune(keep)
@@ -395,7 +402,7 @@ def two_party_crawl(c0: KeyCollection, c1: KeyCollection, threshold: float, ncli
             if not (record or expect_counts is not None):
                 continue
             if not last:
-                res.counts.append(((s0.astype(object) - s1.astype(object)) % FE_P).astype(np.uint64))
+                res.counts.append(((s0.astype(object) - s1.astype(object)) % ((1 << 32) if ring32 else FE_P)).astype(np.uint64))
             else:
                 res.counts.append(np.array([((a % FE255_P) - (b % FE255_P)) % FE255_P for a, b in zip(s0, s1)],
                                            np.uint64))

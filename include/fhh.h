@@ -193,6 +193,11 @@ int fhh_export_states(fhh_ctx* ctx, uint64_t* n_nodes, uint8_t* seeds, uint8_t* 
 
 /* keep_values (collect.rs:945-964): v = v0 - v1 mod p_FE; keep iff v >= threshold. */
 int fhh_keep_values(uint64_t threshold, const uint64_t* vals0, const uint64_t* vals1, uint64_t n, uint8_t* keep);
+/* keep_values for the servers' Z_2^32 sums (fhh_party_node_sums after a form-2 FE level, fhh_gb_cfg.form):
+ * keep[i] = ((vals0[i] - vals1[i]) mod 2^32) >= threshold. Precondition: the client total is below 2^32, so
+ * the count v0 - v1 is the same integer as in FE. FHH_E_ARG (nothing written) if the threshold or any value
+ * is 2^32 or more: such values are not Z_2^32 sums (FE sums fed in by mistake). */
+int fhh_keep_values_ring32(uint64_t threshold, const uint64_t* vals0, const uint64_t* vals1, uint64_t n, uint8_t* keep);
 /* keep_values_last (collect.rs:966-989) on FE255 values given as [n][10] u32 LE limbs. */
 int fhh_keep_values_last(uint32_t threshold, const uint32_t* vals0, const uint32_t* vals1, uint64_t n, uint8_t* keep);
 /* final_values (collect.rs:1007-1029): out [n][8] canonical (v0 - v1 mod p255). */
@@ -588,10 +593,12 @@ int fhh_gt_cot_host(fhh_ctx* ctx, uint64_t n, uint32_t bits, const uint8_t* gb_b
                     uint32_t mask, uint64_t gate_base, const uint8_t base_seeds[128 * 2 * 16],
                     const uint8_t base_choice[16], uint64_t ctr_off, uint8_t* ev_zero, uint8_t* ev_active,
                     uint64_t* msgs, uint64_t* gb_share, uint64_t* ev_share);
-/* r06: the same table with its shares in Z_2^32 (bits <= 2; fhh_sim_config.table_ring32's form): row 0's value
- * is lo32 of its hash, pair = (v, v +- 1 mod 2^32), rows 1 .. 2^b - 1 send lo32(hash) ^ pair[o_r] (4 B);
- * msgs / gb_share / ev_share as above, each value zero-extended to u64 (gb - ev = eq mod 2^32). Oracle:
- * orc_gt_garble_ring32 / orc_gt_eval_ring32. */
+/* r06: the same table with its shares in Z_2^32 (bits <= 4; the party ABI's form 2, and at bits <= 2
+ * fhh_sim_config.table_ring32's form): row 0's value is lo32 of its hash, pair = (v, v +- 1 mod 2^32), rows
+ * 1 .. 2^b - 1 send lo32(hash) ^ pair[o_r] (4 B); msgs / gb_share / ev_share as above, each value zero-extended
+ * to u64 (gb - ev = eq mod 2^32). bits <= 2 on the tile-major kernels, bits = 3, 4 on the row-major
+ * k_gt_garble_r32 / k_gt_eval_r32 (u32 messages and node values on the device). Oracle: orc_gt_garble_ring32 /
+ * orc_gt_eval_ring32. */
 int fhh_gt_cot_ring32_host(fhh_ctx* ctx, uint64_t n, uint32_t bits, const uint8_t* gb_bits, const uint8_t* ev_bits,
                            uint32_t mask, uint64_t gate_base, const uint8_t base_seeds[128 * 2 * 16],
                            const uint8_t base_choice[16], uint64_t ctr_off, uint8_t* ev_zero, uint8_t* ev_active,
@@ -629,7 +636,17 @@ int fhh_gt_cot_ring32_host(fhh_ctx* ctx, uint64_t n, uint32_t bits, const uint8_
  * y1 0 B; u2 / y2: 0 B at the FE levels, FieldElm level: U (as u1) and 16 B per OT. A follow-on chunk
  * (child_begin != 0) must keep the form of the level's first chunk (FHH_E_STATE otherwise: the level's
  * storage follows the form), and the shards of a multi-device ctx must run a level in one form
- * (fhh_party_node_sums: "shards disagree"). Each server's node values
+ * (fhh_party_node_sums: "shards disagree").
+ * form = 2 (opt-in; both parties AND the leader must be told): the FE levels' garbled table with its shares in
+ * Z_2^32 instead of FE (fhh_gt_cot_ring32_host), for 2d <= 4 only — FHH_E_ARG from both *_ot_labels calls at
+ * 2d > 4, where there is no table and the circuit has no ring form. At an FE level the labels OT, npad, the
+ * counters and the gate tweaks are exactly form 0's; gc is the table's rows 1 .. 2^(2d) - 1 as u32, SoA
+ * [row][tests], (2^(2d) - 1) x 4 x tests bytes (half of form 0's; a row starts at byte 4 r tests, 4-B aligned
+ * only); u2 / y2 are empty. The FieldElm level is identical to form 0. After a form-2 FE level
+ * fhh_party_node_sums writes uint64_t[C], each the party's sum mod 2^32 zero-extended (a multi-device ctx: the
+ * shards' sums added mod 2^32), and the leader thresholds v0 - v1 mod 2^32 with fhh_keep_values_ring32, NOT
+ * fhh_keep_values: the count is the same integer as long as the client total is below 2^32.
+ * Each server's node values
  * (the garbler's r1 = v + mask, the evaluator's share output) stay on its device; fhh_party_node_sums sums them: non-last
  * level sums [C] canonical FE, last level [C][10] unreduced + [C][8] canonical FieldElm (the
  * frontier_last values). For a multi-device ctx run each shard (fhh_shard_ctx) with its own channel,
@@ -647,7 +664,8 @@ int fhh_gt_cot_ring32_host(fhh_ctx* ctx, uint64_t n, uint32_t bits, const uint8_
 typedef struct fhh_gb_cfg {
     uint32_t mask;                       /* the chunk's mask bit (equalitytest.rs:38-43)           */
     uint32_t form;                       /* FE levels: 0 = the garbled table where 2d <= 4 (r05d),
-                                            1 = the half-gates circuit (r05c); both parties alike  */
+                                            1 = the half-gates circuit (r05c), 2 = the garbled table
+                                            with Z_2^32 shares (2d <= 4 only); both parties alike  */
     uint8_t base_chosen[2][128][16];     /* per OT kind (0 labels, 1 shares — read at tree_crawl_last
                                             only since r05c): k_i^{s_i} from the                    */
     uint8_t base_choice[2][16];          /* base OTs, and s (bit i % 8 of byte i / 8); the labels
@@ -676,8 +694,8 @@ int fhh_ev_evaluate(fhh_ctx* ctx, const uint8_t* gc_msg_dev, uint64_t gc_msg_byt
                     uint64_t y_bytes, const uint8_t** u_dev, uint64_t* u_bytes);
 int fhh_gb_ot_shares(fhh_ctx* ctx, const uint8_t* u_dev, uint64_t u_bytes, const uint8_t** y_dev, uint64_t* y_bytes);
 int fhh_ev_ot_shares(fhh_ctx* ctx, const uint8_t* y_dev, uint64_t y_bytes);
-/* sums_a = uint64_t[C] (non-last level) or uint32_t[C][10] unreduced (last); sums_b = NULL or
- * uint32_t[C][8] canonical (last level) */
+/* sums_a = uint64_t[C] (non-last level: canonical FE, or after a form-2 level the sum mod 2^32) or
+ * uint32_t[C][10] unreduced (last); sums_b = NULL or uint32_t[C][8] canonical (last level) */
 int fhh_party_node_sums(fhh_ctx* ctx, void* sums_a, void* sums_b);
 /* bytes this ctx sent in the level so far (its outgoing messages) */
 int fhh_party_bytes_sent(const fhh_ctx* ctx, uint64_t* bytes);
