@@ -248,6 +248,12 @@ class KeyCollection:
         instead of the occupancy-derived grid. `set_variant` drops the override: call it first."""
         self._chk(lib().fhh_set_expand_grid(self._h, blocks))
 
+    def set_table_row_major(self, on: bool):
+        """Tests / diagnostics: the level loop and gc.table_cot run the garbled tables of b = 3, 4 bits (d = 2) on
+        the row-major labels (the transpose pass + the row-major kernels) instead of the default tile-major
+        kernels. Same outputs."""
+        self._chk(lib().fhh_set_table_row_major(self._h, 1 if on else 0))
+
     def reset_stats(self):
         self._chk(lib().fhh_reset_stats(self._h))
 

@@ -113,6 +113,9 @@ struct fhh_ctx {
     uint64_t client_base = 0;
     int variant = 0;              // k_expand variant (fhh_set_variant)
     int grid = 0;
+    // fhh_set_table_row_major: 1 = b = 3, 4 tables of the level loop and fhh_gt_cot*_host on k_ot_rows_out's
+    // row-major labels; 0 (default, profiles/gt_tm_wide/) = the tile-major kernels
+    int table_row_major = 0;
     uint32_t loop_cap_hint = 0;   // device loop: capacity the previous crawl grew to
     DevBuf work_counter;          // dynamic item distribution
     uint32_t expand_seq = 0;      // k_expand launches on work_counter (its counter slot alternates)

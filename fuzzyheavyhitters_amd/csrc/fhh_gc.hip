@@ -21,6 +21,7 @@
 #include "aes_keyed.h"
 #include "cot_fe.h"
 #include "bitslice.h"
+#include "gt_window.h"
 
 namespace fhh {
 
@@ -437,6 +438,11 @@ __device__ __forceinline__ uint64_t fe_dec(uint64_t v) { return v ? v - 1 : kOtF
 #ifndef FHH_GT_GARBLE_U
 #define FHH_GT_GARBLE_U 1   // tests per lane per pass (A/B knob)
 #endif
+// rows per AES pass of k_gt_garble_tm<3|4> (A/B knob, honoured like the others only in an explicit A/B build): 2.
+// Passes of 4 blocks, k_gt_garble's form, spilled 9 - 20 VGPRs of the 128 a 1024-thread workgroup leaves a lane
+#ifndef FHH_GT_TM_WIDE_NB
+#define FHH_GT_TM_WIDE_NB 2
+#endif
 #ifndef FHH_GT_EVAL_U
 #define FHH_GT_EVAL_U 2
 #endif
@@ -775,6 +781,40 @@ hipError_t launch_ring32_child_sums(const uint32_t* vals, uint64_t n, uint64_t C
     return hipSuccess;
 }
 
+// The level loop's form of the sums above (row-major Z_2^32 table, d = 2): child c of the chunk's G adds its
+// row's u64 total to partials[(g_off + c) * 4 + slot] (slot 0 the garbler's low sum, 2 the evaluator's: the
+// tile-major kernels' fused layout, which k_prune reads mod 2^32); children past the level's C (ctl) are skipped.
+__global__ __launch_bounds__(kRingSumThreads) void k_ring32_child_partials(const uint32_t* vals, uint64_t n, uint64_t c0,
+                                                                           const LoopCtl* ctl, uint64_t g_off,
+                                                                           uint64_t* partials, uint32_t slot) {
+    const uint64_t c = c0 + blockIdx.y;
+    if (ctl && (ctl->abort || g_off + c >= ctl->C)) return;
+    const uint64_t lo = (uint64_t)blockIdx.x * kRingSumSlice;
+    const uint64_t hi = lo + kRingSumSlice < n ? lo + kRingSumSlice : n;
+    const uint32_t* row = vals + c * n;
+    uint64_t acc = 0;
+    for (uint64_t i = lo + threadIdx.x; i < hi; i += kRingSumThreads) acc += row[i];
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off, 64);
+    if ((threadIdx.x & 63) == 0 && acc)
+        atomicAdd(reinterpret_cast<unsigned long long*>(partials + (g_off + c) * 4 + slot), (unsigned long long)acc);
+}
+
+hipError_t launch_ring32_child_partials(const uint32_t* vals, uint64_t n, uint64_t G, const LoopCtl* ctl, uint64_t g_off,
+                                        uint64_t* partials, uint32_t slot, hipStream_t stream) {
+    if (n == 0 || G == 0) return hipSuccess;
+    if (!vals || !partials) return hipErrorInvalidValue;
+    const uint64_t per = (n + kRingSumSlice - 1) / kRingSumSlice;
+    for (uint64_t c0 = 0; c0 < G; c0 += 65535) {   // grid.y holds 65535 children per launch
+        const uint64_t cc = G - c0 < 65535 ? G - c0 : 65535;
+        hipLaunchKernelGGL(k_ring32_child_partials, dim3((uint32_t)per, (uint32_t)cc), dim3(kRingSumThreads), 0, stream,
+                           vals, n, c0, ctl, g_off, partials, slot);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
 // ---- r06: the garbled table on the labels OT's tile-major matrices ------------------------------
 // k_gt_garble / k_gt_eval read one row-major 16-B label per (test, bit), which k_ot_rows_out produced
 // from the tile-major Q / T the OT expands write: 32 B of HBM per OT and party (read + write) and a
@@ -790,7 +830,6 @@ hipError_t launch_ring32_child_sums(const uint32_t* vals, uint64_t n, uint64_t C
 // 2^b rows of one test per pass, as k_gt_garble; evaluator: two rounds' 4 tests per pass). Identical
 // outputs to k_ot_rows_out + k_gt_garble / k_gt_eval (oracle orc_gt_garble / orc_gt_eval).
 constexpr int kGtWaves = kGcThreads / 64;
-constexpr uint32_t kGtTileWords = 128 * 16;   // one 512-OT tile of Q / T: 128 rows x 16 words
 
 // exchange round r (x[0..7] = the tile's x[8 r .. 8 r + 7]): lane l receives OTs 32 qq + 8 r + (l & 7),
 // qq = (l >> 3) + 8 u, u < 2; then x moves down by 8 (a rolled round loop keeps x in registers). Stage
@@ -844,8 +883,25 @@ __device__ __forceinline__ uint32_t gt_tile_test(uint32_t lane, int r, int u) {
 template <int B>
 __device__ __forceinline__ void gt_tile_rows(const GcArgs& a, uint64_t g, uint32_t iw, uint32_t Npt, uint32_t lane,
                                              uint32_t (&x)[32]) {
-    static_assert(B == 1 || B == 2, "gt_tile_rows: b <= 2");
+    static_assert(B >= 1 && B <= kGtTmMaxBits, "gt_tile_rows: b <= 4");
     const uint32_t q = lane >> 2, rg = lane & 3;
+    if constexpr (B > kGtTmPadBits) {
+        // b = 3, 4 (Npad = 64 nw, any nw; Npt = ceil(nw / 8) windows per group): bit k's 512-test window starts
+        // at 32-OT word column (g b + k) 2 nw + 16 iw of the matrix, any even column, so it may straddle two
+        // tiles: lane (q, rg) reads word (col + q) % 16 of tile (col + q) / 16. Words whose 32 tests lie at or
+        // beyond Npad belong to the next bit's or group's OTs (past the last row: beyond the matrix) and are never
+        // read: their lanes take the window's last live word instead. Invariant: a lane holds one word's 32 tests
+        // through the transpose and the exchange deals whole tests, so such a lane's data reach only tests
+        // i >= Npad, and i >= Npad implies i >= N: no live test sees them, and no dead test is stored or summed.
+        // S = e_0 ^ sigma(e_1) ^ sigma^2(e_2) ^ sigma^3(e_3): row r of sigma^k(e) is row r - k of e; the k rows
+        // shifted out, 128 - k + j (j < k), come back by x^128 = x^7 + x^2 + x + 1 into rows j, j + 1, j + 2,
+        // j + 7 — all within rows 0 .. 9, lane group rg = 0.
+        // (gt_window.h: the addressing and the fold, shared with the host self-test)
+        const uint32_t nw2 = 2 * a.nw;
+        gt_window_fold<B>(reinterpret_cast<const uint32_t*>(a.ev_labels), g, nw2, gt_window_word(16 * iw + q, nw2), rg, x);
+        transpose32(x);
+        return;
+    }
     const uint32_t* t0 = reinterpret_cast<const uint32_t*>(a.ev_labels) + (((uint64_t)g * B) * Npt + iw) * kGtTileWords + q;
 #pragma unroll
     for (int i = 0; i < 32; i++) x[i] = __builtin_nontemporal_load(t0 + (32 * rg + i) * 16);
@@ -870,6 +926,16 @@ template <int B>
 __device__ __forceinline__ void gt_tile_colours(const GcArgs& a, uint64_t g, uint32_t iw, uint32_t Npt, uint32_t lane,
                                                 uint32_t (&cw)[B][2]) {
     const uint32_t* lab = reinterpret_cast<const uint32_t*>(a.ev_labels);
+    if constexpr (B > kGtTmPadBits) {   // the window's words at their offset in the tiles (gt_tile_rows)
+#pragma unroll
+        for (int k = 0; k < B; k++)
+#pragma unroll
+            for (int u = 0; u < 2; u++) {
+                const uint32_t w = gt_window_word(16 * iw + (lane >> 3) + 8 * u, 2 * a.nw);
+                cw[k][u] = lab[gt_col_offset(gt_window_col(g, B, k, 2 * a.nw, w))];
+            }
+        return;
+    }
 #pragma unroll
     for (int k = 0; k < B; k++)
 #pragma unroll
@@ -893,7 +959,61 @@ __device__ __forceinline__ uint32_t gt_row_of(const uint32_t (&cw)[B][2], int r,
 template <int B, bool GARBLER>
 __device__ __forceinline__ void gt_tile_keys(const GcArgs& a, uint64_t g, uint32_t iw, uint32_t Npt, uint32_t* st,
                                              uint32_t lane, const uint32_t (&Dk)[B][4], uint32_t (&S)[8][4],
-                                             uint32_t& col) {
+                                             uint32_t& col, uint32_t& xcol) {
+    if constexpr (B > kGtTmPadBits) {
+        // b = 3, 4: the colour and plane words (2 b each) are packed into col and xcol (~x_k of test j at bit
+        // 4 j + k) BEFORE the window's 32 b row words are loaded, so only two words stay live beside them. The
+        // keys stay raw (the fold of the E_k): the garbler's Delta terms XOR_k (x_k ? 0 : sigma^k(Delta)) join the
+        // row's own, bit k of (r ^ col ^ xcol), where the rows' keys are made
+        xcol = 0;
+        col = 0;
+        {
+            // (an opaque copy of the lane: the word indices and shifts below are then made per tile, a few VALU, instead
+            // of being hoisted out of the tile loop, where they stayed live across the AES and spilled)
+            uint32_t ln = lane;
+            asm volatile("" : "+v"(ln));
+            uint32_t cw[B][2], nx[B][2];
+            gt_tile_colours<B>(a, g, iw, Npt, ln, cw);
+            if constexpr (GARBLER) {
+#pragma unroll
+                for (int k = 0; k < B; k++)
+#pragma unroll
+                    for (int u = 0; u < 2; u++) {   // the window's tail beyond the plane row: dead tests
+                        const uint32_t w = gt_window_word(16 * iw + (ln >> 3) + 8 * u, 2 * a.nw);
+                        nx[k][u] = ~reinterpret_cast<const uint32_t*>(
+                            a.gb_planes)[((a.g_off + g) * B + k) * (2 * (uint64_t)a.nw) + w];
+                        cw[k][u] ^= nx[k][u];   // Z_k's colour: Delta's colour bit is 1
+                    }
+            }
+#pragma unroll
+            for (int r = 0; r < 4; r++)
+#pragma unroll
+                for (int u = 0; u < 2; u++) {
+                    col |= gt_row_of<B>(cw, r, u, ln) << (4 * (2 * r + u));
+                    if constexpr (GARBLER) xcol |= gt_row_of<B>(nx, r, u, ln) << (4 * (2 * r + u));
+                }
+        }
+        // pin the packing here: left alone the compiler sinks it below the exchange rounds, where col is first
+        // used, and carries (and spills) the 4 b raw words across the row loads instead of these two
+        asm volatile("" : "+v"(col), "+v"(xcol));
+        uint32_t x[32];
+        gt_tile_rows<B>(a, g, iw, Npt, lane, x);
+#pragma unroll 1
+        for (int r = 0; r < 4; r++) {
+            uint32_t o[2][4];
+            gt_tile_round(st, x, lane, o);
+#pragma unroll
+            for (int j = 0; j < 6; j++)
+#pragma unroll
+                for (int c = 0; c < 4; c++) S[j][c] = S[j + 2][c];
+#pragma unroll
+            for (int c = 0; c < 4; c++) {
+                S[6][c] = o[0][c];
+                S[7][c] = o[1][c];
+            }
+        }
+        return;
+    }
     uint32_t x[32], cw[B][2], nx[B][2];
     gt_tile_rows<B>(a, g, iw, Npt, lane, x);
     gt_tile_colours<B>(a, g, iw, Npt, lane, cw);
@@ -938,15 +1058,17 @@ __device__ __forceinline__ void gt_tile_keys(const GcArgs& a, uint64_t g, uint32
     }
 }
 
-// (b <= 2, the d = 1 tests of the metric's configuration; d = 2 keeps k_ot_rows_out + the row-major kernels)
+// (b <= 2: whole tiles, one AES pass per test; b = 3, 4: windows at any word offset, 2^b rows in passes of FHH_GT_TM_WIDE_NB = 2 AES blocks)
 template <int B, bool RING = false>   // RING: GcArgs::ring32 (a separate instantiation: no FE code beside it)
 __global__ __launch_bounds__(kGcThreads) void k_gt_garble_tm(GcArgs a) {
-    static_assert(B <= 2, "the tile-major garbler takes b <= 2");
+    static_assert(B <= kGtTmMaxBits, "the tile-major garbler takes b <= 4");
     __shared__ uint32_t tbl_gc[GcTab::kWords];
     __shared__ __attribute__((aligned(16))) uint32_t stage[kGtWaves][512];
-    const uint32_t lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    // (b = 3, 4: the wave index as a scalar, so the tile's index arithmetic stays out of the VGPRs)
+    const uint32_t lane = threadIdx.x & 63,
+                   wv = B > kGtTmPadBits ? (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) : threadIdx.x >> 6;
     const uint64_t n_act = gc_active(a);
-    const uint32_t Npt = a.nw / 8;   // 512-test tiles per group
+    const uint32_t Npt = (B > kGtTmPadBits ? a.nw + 7 : a.nw) / 8;   // 512-test tiles (b > 2: windows) per group
     const uint64_t tiles = (n_act / a.N) * Npt;
     if ((uint64_t)blockIdx.x * kGtWaves >= tiles) return;   // no tiles for this workgroup: skip the table fill
     gc_fill(tbl_gc);
@@ -963,12 +1085,114 @@ __global__ __launch_bounds__(kGcThreads) void k_gt_garble_tm(GcArgs a) {
         for (int c = 0; c < 4; c++) Dk[k][c] = Dk[k - 1][c];
         gf_dbl(Dk[k]);
     }
+    // b = 3, 4: (group, window) of the wave's tile stepped along with wt — the 64-bit division per tile kept its
+    // reciprocal constants in VGPRs across the whole loop
+    uint64_t g_next = 0, g_step = 0;
+    uint32_t iw_next = 0, iw_step = 0;
+    if constexpr (B > kGtTmPadBits) {
+        const uint64_t w0 = (uint64_t)blockIdx.x * kGtWaves + wv, ws = (uint64_t)gridDim.x * kGtWaves;
+        g_next = w0 / Npt;
+        iw_next = (uint32_t)(w0 - g_next * Npt);
+        g_step = ws / Npt;
+        iw_step = (uint32_t)(ws - g_step * Npt);
+    }
     for (uint64_t wt = (uint64_t)blockIdx.x * kGtWaves + wv; wt < tiles; wt += (uint64_t)gridDim.x * kGtWaves) {
-        const uint64_t g = wt / Npt;
-        const uint32_t iw = (uint32_t)(wt - g * Npt);
-        uint32_t S[8][4], col;
-        gt_tile_keys<B, true>(a, g, iw, Npt, stage[wv], lane, Dk, S, col);
+        uint64_t g;
+        uint32_t iw;
+        if constexpr (B > kGtTmPadBits) {
+            g = g_next;
+            iw = iw_next;
+            g_next += g_step;
+            iw_next += iw_step;
+            if (iw_next >= Npt) {
+                iw_next -= Npt;
+                g_next++;
+            }
+        } else {
+            g = wt / Npt;
+            iw = (uint32_t)(wt - g * Npt);
+        }
+        uint32_t S[8][4], col, xcol;
+        gt_tile_keys<B, true>(a, g, iw, Npt, stage[wv], lane, Dk, S, col, xcol);
         uint64_t acc_lo = 0, acc_hi = 0;   // node_partials: this lane's live node values' limbs
+        if constexpr (B > kGtTmPadBits) {   // 2^b rows in passes of NBW AES blocks; RING: Z_2^32 only
+constexpr uint32_t NBW = FHH_GT_TM_WIDE_NB;   // rows per AES pass
+#pragma unroll 1
+            for (int j = 0; j < 8; j++) {
+                const uint32_t i = 512 * iw + gt_tile_test(lane, j >> 1, j & 1);
+                const bool live = i < a.N;
+                const uint64_t t = g * a.N + i;
+                {   // the tweak goes into S[0] itself (the key of this test only: S rotates it away below)
+                    const uint64_t tw = a.gate_base + a.g_off * a.N + t;   // the test's index in the whole level
+                    S[0][0] ^= (uint32_t)tw;
+                    S[0][1] ^= (uint32_t)(tw >> 32);
+                }
+                const uint32_t cl = col & (R - 1);
+                const uint32_t rstar = ~cl & (R - 1);   // the row whose z are all 1 (eq = 1)
+                // row 0's value (pass 0): the pair is (v, v +- 1), rebuilt where a row needs it
+                typename std::conditional<RING, uint32_t, uint64_t>::type v = 0;
+#pragma unroll 1
+                for (uint32_t pass = 0; pass < R / NBW; pass++) {
+                    uint32_t h[NBW][4];
+#pragma unroll
+                    for (uint32_t jj = 0; jj < NBW; jj++) {
+                        // z_k of the row = bit k of r ^ col; ^ ~x_k: the test's own Delta terms (gt_tile_keys)
+                        const uint32_t flip = (NBW * pass + jj) ^ cl ^ (xcol & (R - 1));
+#pragma unroll
+                        for (int c = 0; c < 4; c++) {
+                            uint32_t w = S[0][c];
+#pragma unroll
+                            for (int k = 0; k < B; k++) w ^= ((flip >> k) & 1u) ? Dk[k][c] : 0u;
+                            h[jj][c] = w;
+                        }
+                    }
+                    aes0_mmo_tab<DevOpsX, GcTab, NBW>(h, tbl_gc, b0, b1);   // cr_hash: pi(K) ^ K
+#pragma unroll
+                    for (uint32_t jj = 0; jj < NBW; jj++) {
+                        const uint32_t q = NBW * pass + jj;
+                        const uint32_t o_r = (uint32_t)(q == rstar) ^ a.mask;
+                        if (jj == 0 && pass == 0) {   // row 0's value pair[o_0] fixes v
+                            if constexpr (RING) {
+                                const uint32_t h32 = h[0][0];
+                                const uint32_t v32 = o_r == 0 ? h32 : (a.mask ? h32 - 1u : h32 + 1u);
+                                v = v32;
+                                const uint32_t r1 = a.mask ? v32 + 1u : v32;   // r1 = v + mask
+                                if (live && a.node_partials) acc_lo += r1;
+                                else if (live) a.sh_gb[t] = r1;
+                            } else {
+                                const uint64_t hv = ot_fe_of_u128((uint64_t)h[0][0] | ((uint64_t)h[0][1] << 32),
+                                                                  (uint64_t)h[0][2] | ((uint64_t)h[0][3] << 32));
+                                v = o_r == 0 ? hv : (a.mask ? fe_dec(hv) : fe_inc(hv));
+                                const uint64_t r1 = a.mask ? fe_inc(v) : v;   // r1 = v + mask
+                                if (live && a.node_partials) {
+                                    acc_lo += r1 & 0xFFFFFFFFull;
+                                    acc_hi += r1 >> 32;
+                                } else if (live) {
+                                    a.sh_gb[t] = r1;
+                                }
+                            }
+                        } else if (live) {
+                            if constexpr (RING) {
+                                const uint32_t v32 = (uint32_t)v;
+                                const uint32_t pr = o_r ? (a.mask ? v32 + 1u : v32 - 1u) : v32;
+                                reinterpret_cast<uint32_t*>(a.gt_msgs)[(uint64_t)(q - 1) * n + t] = h[jj][0] ^ pr;
+                            } else {
+                                const uint64_t pr = o_r ? (a.mask ? fe_inc(v) : fe_dec(v)) : v;
+                                a.gt_msgs[(uint64_t)(q - 1) * n + t] = ((uint64_t)h[jj][0] | ((uint64_t)h[jj][1] << 32)) ^ pr;
+                            }
+                        }
+                    }
+                }
+#pragma unroll
+                for (int jj = 0; jj < 7; jj++)
+#pragma unroll
+                    for (int c = 0; c < 4; c++) S[jj][c] = S[jj + 1][c];
+                col >>= 4;
+                xcol >>= 4;
+            }
+            if (a.node_partials) gt_add_partials(a.node_partials, a.node_off + a.g_off + g, 0, acc_lo, acc_hi, lane);
+            continue;
+        }
 #pragma unroll 1
         for (int j = 0; j < 8; j++) {   // test j = (r, u) = (j >> 1, j & 1); S and col rotate by one test
             const uint32_t i = 512 * iw + gt_tile_test(lane, j >> 1, j & 1);
@@ -1045,24 +1269,50 @@ __global__ __launch_bounds__(kGcThreads) void k_gt_garble_tm(GcArgs a) {
 // profiles/r06/ring32/)
 template <int B>
 __global__ __launch_bounds__(kGcThreads) void k_gt_eval_tm(GcArgs a) {
-    static_assert(B <= 2, "the tile-major evaluator takes b <= 2");
+    static_assert(B <= kGtTmMaxBits, "the tile-major evaluator takes b <= 4");
     __shared__ uint32_t tbl_gc[GcTab::kWords];
     __shared__ __attribute__((aligned(16))) uint32_t stage[kGtWaves][512];
-    const uint32_t lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    // (b = 3, 4: the wave index as a scalar, so the tile's index arithmetic stays out of the VGPRs)
+    const uint32_t lane = threadIdx.x & 63,
+                   wv = B > kGtTmPadBits ? (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) : threadIdx.x >> 6;
     const uint64_t n_act = gc_active(a);
-    const uint32_t Npt = a.nw / 8;
+    const uint32_t Npt = (B > kGtTmPadBits ? a.nw + 7 : a.nw) / 8;
     const uint64_t tiles = (n_act / a.N) * Npt;
     if ((uint64_t)blockIdx.x * kGtWaves >= tiles) return;
     gc_fill(tbl_gc);
     uint32_t b0, b1;
     GcTab::bases(lane, b0, b1);
     const uint64_t n = a.G * a.N;
+    // b = 3, 4: (group, window) of the wave's tile stepped along with wt — the 64-bit division per tile kept its
+    // reciprocal constants in VGPRs across the whole loop
+    uint64_t g_next = 0, g_step = 0;
+    uint32_t iw_next = 0, iw_step = 0;
+    if constexpr (B > kGtTmPadBits) {
+        const uint64_t w0 = (uint64_t)blockIdx.x * kGtWaves + wv, ws = (uint64_t)gridDim.x * kGtWaves;
+        g_next = w0 / Npt;
+        iw_next = (uint32_t)(w0 - g_next * Npt);
+        g_step = ws / Npt;
+        iw_step = (uint32_t)(ws - g_step * Npt);
+    }
     for (uint64_t wt = (uint64_t)blockIdx.x * kGtWaves + wv; wt < tiles; wt += (uint64_t)gridDim.x * kGtWaves) {
-        const uint64_t g = wt / Npt;
-        const uint32_t iw = (uint32_t)(wt - g * Npt);
-        uint32_t S[8][4], col;
+        uint64_t g;
+        uint32_t iw;
+        if constexpr (B > kGtTmPadBits) {
+            g = g_next;
+            iw = iw_next;
+            g_next += g_step;
+            iw_next += iw_step;
+            if (iw_next >= Npt) {
+                iw_next -= Npt;
+                g_next++;
+            }
+        } else {
+            g = wt / Npt;
+            iw = (uint32_t)(wt - g * Npt);
+        }
+        uint32_t S[8][4], col, xcol;
         const uint32_t nod[B][4] = {};
-        gt_tile_keys<B, false>(a, g, iw, Npt, stage[wv], lane, nod, S, col);
+        gt_tile_keys<B, false>(a, g, iw, Npt, stage[wv], lane, nod, S, col, xcol);
         uint64_t acc_lo = 0, acc_hi = 0;
 #pragma unroll 1
         for (int r = 0; r < 4; r++) {   // round r's 2 tests: 2 AES blocks in lockstep (4 spilled 6 VGPRs)
@@ -1117,8 +1367,8 @@ static hipError_t gt_launch(const GcArgs& a, bool garble, hipStream_t stream) {
     e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
     if (e != hipSuccess) return e;
     const uint64_t n = a.G * a.N;
-    if constexpr (B <= 2) if (a.lab_tm) {   // r06: one wave per 512-test tile, one 160 KiB workgroup per CU
-        const uint64_t tiles = a.G * (a.nw / 8), need = (tiles + kGtWaves - 1) / kGtWaves;
+    if constexpr (B <= kGtTmMaxBits) if (a.lab_tm) {   // r06: one wave per 512-test tile, one 160 KiB workgroup per CU
+        const uint64_t tiles = a.G * ((B > kGtTmPadBits ? a.nw + 7 : a.nw) / 8), need = (tiles + kGtWaves - 1) / kGtWaves;
         const int grid = (int)(need < (uint64_t)cus ? (need ? need : 1) : (uint64_t)cus);
         if (garble && a.ring32) hipLaunchKernelGGL((k_gt_garble_tm<B, true>), dim3(grid), dim3(kGcThreads), 0, stream, a);
         else if (garble) hipLaunchKernelGGL((k_gt_garble_tm<B, false>), dim3(grid), dim3(kGcThreads), 0, stream, a);
@@ -1127,7 +1377,7 @@ static hipError_t gt_launch(const GcArgs& a, bool garble, hipStream_t stream) {
     }
     const uint64_t need = (n + kGcThreads - 1) / kGcThreads;
     const int grid = (int)(need < (uint64_t)cus * 8 ? (need ? need : 1) : (uint64_t)cus * 8);
-    if constexpr (B > kGtTmMaxBits) if (a.ring32) {   // Z_2^32 shares on the row-major labels (b = 3, 4)
+    if constexpr (B > kGtTmPadBits) if (a.ring32) {   // Z_2^32 shares on the row-major labels (b = 3, 4)
         if (garble) hipLaunchKernelGGL(k_gt_garble_r32<B>, dim3(grid), dim3(kGcThreads), 0, stream, a);
         else hipLaunchKernelGGL(k_gt_eval_r32<B>, dim3(grid), dim3(kGcThreads), 0, stream, a);
         return hipGetLastError();
@@ -1141,10 +1391,11 @@ static hipError_t gt_dispatch(const GcArgs& a, bool garble, hipStream_t stream) 
     if (a.G * a.N == 0) return hipSuccess;
     if (!a.gt_msgs || (!(garble ? a.sh_gb : a.sh_ev) && !(a.lab_tm && a.node_partials)) || !a.ev_labels)
         return hipErrorInvalidValue;
-    // r06 tile-major labels: 512-test tiles per group, b <= 2 (gt_tm_bits)
-    if (a.lab_tm && (a.nw % 8 != 0 || a.bits > (uint32_t)kGtTmMaxBits)) return hipErrorInvalidValue;
-    // Z_2^32: the tile-major kernels at b <= 2, k_gt_garble_r32 / k_gt_eval_r32 on row-major labels at b = 3, 4
-    if (a.ring32 && !a.lab_tm && a.bits <= (uint32_t)kGtTmMaxBits) return hipErrorInvalidValue;
+    // tile-major labels: b <= 4; whole 512-test tiles per group at b <= 2 only (b = 3, 4: windows at any nw)
+    if (a.lab_tm && (a.bits > (uint32_t)kGtTmMaxBits || (a.bits <= (uint32_t)kGtTmPadBits && a.nw % 8 != 0)))
+        return hipErrorInvalidValue;
+    // Z_2^32: the tile-major kernels at b <= 4; b = 3, 4 also k_gt_garble_r32 / k_gt_eval_r32 on row-major labels
+    if (a.ring32 && !a.lab_tm && a.bits <= (uint32_t)kGtTmPadBits) return hipErrorInvalidValue;
     switch (a.bits) {
         case 1: return gt_launch<1>(a, garble, stream);
         case 2: return gt_launch<2>(a, garble, stream);

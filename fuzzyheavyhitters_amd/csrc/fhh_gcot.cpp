@@ -573,9 +573,12 @@ static int gt_cot_host(fhh_ctx* ctx, uint64_t n, uint32_t bits, const uint8_t* g
     // r06: b <= 2 runs the tile-major table kernels on Q / T (the level loop's form), whose OT index wants
     // plane rows of whole 512-client tiles; b = 3, 4 the row-major labels of k_ot_rows_out (Z_2^32 there:
     // k_gt_garble_r32 / k_gt_eval_r32, whose node values are u32)
-    const bool tm = bits <= (uint32_t)kGtTmMaxBits;
+    // (b = 3, 4 tile-major too, on windows at any nw = ceil(n / 64): the OT index stays; fhh_set_table_row_major
+    // keeps them on the row-major labels)
+    const bool tm = bits <= (uint32_t)kGtTmPadBits || !ctx->table_row_major;
     const bool val32 = ring32 && !tm;
-    const uint64_t nw = tm ? (n + 511) / 512 * 8 : (n + 63) / 64, npad = 64 * nw, m = (uint64_t)bits * npad;
+    const uint64_t nw = bits <= (uint32_t)kGtTmPadBits ? (n + 511) / 512 * 8 : (n + 63) / 64, npad = 64 * nw,
+                   m = (uint64_t)bits * npad;
     const uint64_t R = 1ull << bits;
     std::vector<uint64_t> planes[2];
     const uint8_t* src[2] = {gb_bits, ev_bits};
@@ -725,7 +728,7 @@ struct PartyState {
     bool lshare = false;        // r05c (FE levels): the share from the GC output labels, no OT 2
     bool ltable = false;        // r05d (FE levels, bits <= kGtMaxBits): one garbled table per test
     bool lring = false;         // form 2 (ltable): the table's shares, messages and node values in Z_2^32 (u32)
-    bool ltm = false;           // r06 (ltable, bits <= kGtTmMaxBits): the table kernels read the labels OT's
+    bool ltm = false;           // r06 (ltable, bits <= kGtTmPadBits): the table kernels read the labels OT's
                                 // tile-major Q / T (no row transposes); npad / nw = whole 512-client tiles
     // C = this instance's children: the chunk [c_off, c_off + C) of the level's level_C children
     // (child_begin / child_count); covered = children whose OTs are finished
@@ -821,7 +824,9 @@ int party_begin(fhh_ctx* ctx, int role, uint64_t child_begin, uint64_t child_cou
     P.lshare = !P.last;
     P.ltable = P.lshare && P.bits <= (uint32_t)kGtMaxBits && form != 1;   // form 1: the circuit (r05c)
     P.lring = P.ltable && form == 2;   // form 2: the table over Z_2^32 (the FieldElm level is form 0's)
-    P.ltm = P.ltable && P.bits <= (uint32_t)kGtTmMaxBits;
+    // (bits = 3, 4 stay on the row-major labels here whatever fhh_set_table_row_major says: the tile-major
+    // kernels of that width serve the level loop and fhh_gt_cot*_host only)
+    P.ltm = P.ltable && P.bits <= (uint32_t)kGtTmPadBits;
     if (P.ltm) {   // plane rows and the OT index over whole 512-client tiles (both parties alike: n is public)
         P.nw = (ctx->nw + 7) / 8 * 8;
         P.npad = 64 * P.nw;

@@ -1043,13 +1043,17 @@ int sim_crawl_device_loop(fhh_ctx* c0, fhh_ctx* c1, const fhh_sim_config* cfg, u
         if (const char* e = std::getenv("FHH_GC_CHUNK_BYTES")) budget = std::strtoull(e, nullptr, 10);
         // r06: the d = 1 garbled table on the tile-major labels holds ~140 B per test (T, U, Q 96, rows 24,
         // node values 16), not the circuit's ~400: larger chunks, one per level at 1M clients
-        const bool tm_table = cfg->gc == 2 && 2 * d <= (uint32_t)kGtTmMaxBits;
-        const uint64_t per_test = tm_table ? 150ull : 200ull * 2 * d + 2;
+        // d = 2 on the tile-major labels: T, U, Q 3 x 4 x 16 B and 15 rows of 8 B, ~320 B per test (the row-major
+        // path adds both parties' 4 labels and the node values: the circuit's estimate stays)
+        const bool tm_table = cfg->gc == 2 && 2 * d <= (uint32_t)kGtTmMaxBits &&
+                              (2 * d <= (uint32_t)kGtTmPadBits || !c0->table_row_major);
+        const uint64_t per_test = !tm_table ? 200ull * 2 * d + 2 : 2 * d <= (uint32_t)kGtTmPadBits ? 150ull : 320ull;
         gc_groups = std::max<uint64_t>(1, budget / (per_test * std::max<uint64_t>(c0->npad, 1)));
         // the FieldElm level runs the circuit + share C-OT whatever the FE levels run
         gc_groups_last = std::max<uint64_t>(1, budget / ((200ull * 2 * d + 2) * std::max<uint64_t>(c0->npad, 1)));
     }
-    // r06: Z_2^32 table shares at the FE levels (the tile-major table with fused sums, d = 1)
+    // Z_2^32 table shares at the FE levels (2d <= 4): the tile-major table with fused sums, or at d = 2 on the
+    // row-major labels k_gt_garble_r32 / k_gt_eval_r32 with their u32 values summed by k_ring32_child_partials
     const bool ring32 = cfg->table_ring32 && cfg->gc == 2 && cfg->mode == 1 && 2 * d <= (uint32_t)kGtTmMaxBits &&
                         FHH_GT_FUSED_SUMS;
     PhaseClock pc;
@@ -1212,8 +1216,12 @@ int sim_crawl_device_loop(fhh_ctx* c0, fhh_ctx* c1, const fhh_sim_config* cfg, u
                 // whole 512-client tiles: the planes and the OT index take nw_gc = nw rounded up to 8 words
                 const bool lshare = real_ot && pmode == 1;
                 const bool ltable = lshare && bits <= (uint32_t)kGtMaxBits && cfg->gc == 2;   // gc 3: the circuit
-                const bool ltm = ltable && bits <= (uint32_t)kGtTmMaxBits;
-                const uint64_t nw_gc = ltm ? (c0->nw + 7) / 8 * 8 : c0->nw, npad_gc = 64 * nw_gc;
+                // (b = 3, 4: windows at any nw, so nw_gc = nw and the OT indices stay; fhh_set_table_row_major
+                // keeps the row-major labels there)
+                const bool ltm = ltable && bits <= (uint32_t)kGtTmMaxBits &&
+                                 (bits <= (uint32_t)kGtTmPadBits || !c0->table_row_major);
+                const uint64_t nw_gc = ltm && bits <= (uint32_t)kGtTmPadBits ? (c0->nw + 7) / 8 * 8 : c0->nw,
+                               npad_gc = 64 * nw_gc;
                 const size_t plane_bytes = (size_t)C_cap * bits * nw_gc * 8;
                 for (int s = 0; s < 2; s++) HIP_TRY(c0, B.gc_planes[s].ensure(plane_bytes));
                 size_t gc_slot = 0;
@@ -1264,7 +1272,9 @@ int sim_crawl_device_loop(fhh_ctx* c0, fhh_ctx* c1, const fhh_sim_config* cfg, u
                 // ideal OT: the evaluator's active labels [bits][tests]; OT mode: its zero labels (the
                 // labels C-OT's sender messages) at OT index (g bits + j) npad + i (r06 tile-major table: none,
                 // the kernels read Q / T)
-                HIP_TRY(c0, B.gc_evl.ensure(std::max<size_t>((size_t)bits * tests, real_ot && !ltm ? m1 : 0) * 16));
+                HIP_TRY(c0, B.gc_evl.ensure(ltm && bits > (uint32_t)kGtTmPadBits
+                                                ? 16
+                                                : std::max<size_t>((size_t)bits * tests, real_ot && !ltm ? m1 : 0) * 16));
                 HIP_TRY(c0, B.gc_decode.ensure(ltable ? 1 : tests));
                 HIP_TRY(c0, B.gc_out.ensure(ltable ? 1 : tests));
                 for (uint64_t k = 0; k < chunks; k++) {
@@ -1333,13 +1343,18 @@ int sim_crawl_device_loop(fhh_ctx* c0, fhh_ctx* c1, const fhh_sim_config* cfg, u
                         g.gt_msgs = B.gc_msgs.as<uint64_t>();
                         g.node_partials = ltm && FHH_GT_FUSED_SUMS ? part : nullptr;
                         g.node_off = 0;
-                        g.ring32 = ring32 && ltm ? 1u : 0u;
+                        g.ring32 = ring32 ? 1u : 0u;   // (row-major: u32 values [tests] in gc_val, u32 messages)
                         g.sh_gb = fused ? nullptr : B.gc_val[0].as<uint64_t>();
                         HIP_TRY(c0, launch_gt_garble(g, c0->stream));
                         g.ev_labels = ltm ? c0->ot_buf[0].as<uint4>() : B.gc_evact.as<uint4>();
                         g.sh_gb = nullptr;
                         g.sh_ev = fused ? nullptr : B.gc_val[1].as<uint64_t>();
                         HIP_TRY(c0, launch_gt_eval(g, c0->stream));
+                        if (ring32 && !fused)   // the row-major Z_2^32 values into the partials' low sums
+                            for (uint32_t sv = 0; sv < 2; sv++)
+                                HIP_TRY(c0, launch_ring32_child_partials(B.gc_val[sv].as<uint32_t>(), c0->n, Gc,
+                                                                         B.ctl.as<LoopCtl>(), g_off, part, 2 * sv,
+                                                                         c0->stream));
                     } else if (lshare) {
                         for (int sv = 0; sv < 2; sv++) HIP_TRY(c0, B.gc_val[sv].ensure(tests * 8));
                         HIP_TRY(c0, B.gc_y.ensure(tests * 8));
@@ -1400,7 +1415,8 @@ int sim_crawl_device_loop(fhh_ctx* c0, fhh_ctx* c1, const fhh_sim_config* cfg, u
                     // the chunk's children's sums (FE: atomics into the partials k_prune zeroed;
                     // FE255: one store per child)
                     if (pmode == 1) {
-                        if (!(ltm && FHH_GT_FUSED_SUMS)) HIP_TRY(c0, launch_child_sums_fe(ca, part, c0->stream, false));
+                        if (!(ltm && FHH_GT_FUSED_SUMS) && !(ltable && ring32))
+                            HIP_TRY(c0, launch_child_sums_fe(ca, part, c0->stream, false));
                     } else {
                         HIP_TRY(c0, launch_child_sums_fe255(ca, part, c0->stream));
                     }
@@ -2346,6 +2362,14 @@ int fhh_set_expand_grid(fhh_ctx* ctx, int blocks) {
     if (blocks < 1 || blocks > full)
         return ctx->fail(FHH_E_ARG, "set_expand_grid: blocks must be in [1, " + std::to_string(full) + "]");
     ctx->grid = blocks;
+    return FHH_OK;
+}
+
+int fhh_set_table_row_major(fhh_ctx* ctx, int on) {
+    CTX_CHECK(ctx);
+    if (ctx->group) return group_each(ctx, fhh_set_table_row_major, on);
+    if (on != 0 && on != 1) return ctx->fail(FHH_E_ARG, "set_table_row_major: on must be 0 or 1");
+    ctx->table_row_major = on;
     return FHH_OK;
 }
 

@@ -237,8 +237,9 @@ struct GcArgs {
     // values to sh_gb, k_gt_eval reads them and writes the evaluator's to sh_ev
     uint64_t* gt_msgs;
     // r06: 1 = ev_labels is the labels OT's tile-major matrix itself (Q for k_gt_garble, T for k_gt_eval;
-    // fhh_ot.hip ot_tmaj) instead of one row-major label per OT (k_ot_rows_out); needs nw % 8 == 0 (the OT
-    // index (g bits + k) 64 nw + i puts a test's labels at one position of 512-OT tiles)
+    // fhh_ot.hip ot_tmaj) instead of one row-major label per OT (k_ot_rows_out). bits <= kGtTmPadBits needs
+    // nw % 8 == 0 (the OT index (g bits + k) 64 nw + i puts a test's labels at one position of 512-OT tiles);
+    // bits = 3, 4 take any nw (a bit's 512-test window starts at any even word of a tile)
     uint32_t lab_tm;
     // r06 (lab_tm): non-null = the table kernels add their node values' 32-bit limbs per child into
     // node_partials [C][4] u64 (k_child_sums_fe's layout: garbler lo, hi; evaluator lo, hi) by one wave sum
@@ -251,7 +252,9 @@ struct GcArgs {
     uint32_t ring32;
 };
 constexpr int kGtMaxBits = 4;   // 16 rows (d = 2); wider tests keep the half-gates chain
-constexpr int kGtTmMaxBits = 2;   // r06: the table kernels read the tile-major labels (lab_tm) for b <= 2 (d = 1)
+constexpr int kGtTmMaxBits = 4;   // the table kernels read the tile-major labels (lab_tm) for b <= 4 (d <= 2)
+constexpr int kGtTmPadBits = 2;   // b <= 2 (d = 1): plane rows padded to whole 512-client tiles (nw % 8 == 0);
+                                  // b = 3, 4 keep Npad = 64 nw, so their OT indices and the wire stay as they were
 
 struct PruneArgs {
     LoopCtl* ctl;
@@ -414,6 +417,8 @@ hipError_t launch_gt_garble(const GcArgs& a, hipStream_t stream);   // r05d garb
 hipError_t launch_gt_eval(const GcArgs& a, hipStream_t stream);
 // sums[c] += the u32 node values vals [C][n] of child c, as u64 (sums zeroed by the caller; Z_2^32 table, b = 3, 4)
 hipError_t launch_ring32_child_sums(const uint32_t* vals, uint64_t n, uint64_t C, uint64_t* sums, hipStream_t stream);
+hipError_t launch_ring32_child_partials(const uint32_t* vals, uint64_t n, uint64_t G, const LoopCtl* ctl, uint64_t g_off,
+                                        uint64_t* partials, uint32_t slot, hipStream_t stream);
 hipError_t launch_gather_hist(const uint32_t* sizes, uint32_t stride, const uint32_t* const* rows, uint32_t levels,
                               uint32_t* out, uint64_t cap, hipStream_t stream);
 // parity probe of the device loop (fhh_sim_config.probe_*): the pending children's states of a

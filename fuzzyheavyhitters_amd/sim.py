@@ -73,7 +73,7 @@ def sim_crawl(c0: KeyCollection, c1: KeyCollection, threshold: float, nclients_t
     "ideal" with both OTs ideal; "ot-circuit" as "ot" but the half-gates circuit (+ the output-label
     share) at every level instead of the FE levels' garbled table. `ot_ss_k` (gc "ot" / "ot-circuit", r06):
     1 = IKNP OT extension, 2 / 4 = SoftSpoken with k = ot_ss_k (128 / k rows of U on the wire). `table_ring32`
-    (gc "ot", d = 1, r06): the FE levels' garbled table carries Z_2^32 shares (4-B rows) instead of FE ones.
+    (gc "ot", 2d <= 4): the FE levels' garbled table carries Z_2^32 shares (4-B rows) instead of FE ones.
 
     `probe` (parity tests) = {"levels": [...], "clients": [...], "capacity": C_max}: the device
     loop gathers those clients' EvalStates of every pending child right after each listed

@@ -314,7 +314,7 @@ typedef struct fhh_sim_config {
      * wire), 2 or 4 = SoftSpoken with k = ot_ss_k (fhh_cot_extend_ss_host: 128 / k rows, 16 / k B per OT,
      * 2^k - 1 ChaCha12 blocks per chunk and tile at the sender). Same sums. */
     uint32_t ot_ss_k;
-    /* gc = 2, d = 1 (r06): 1 = the FE levels' garbled table carries its shares in Z_2^32 instead of FE (4-B
+    /* gc = 2, 2d <= 4 (d = 1, 2): 1 = the FE levels' garbled table carries its shares in Z_2^32 instead of FE (4-B
      * rows instead of 8: the per-child v0 - v1 is the count either way, < 2^32; the FieldElm level is
      * unchanged). Same sums, keep decisions and heavy hitters. */
     uint32_t table_ring32;
@@ -587,18 +587,20 @@ int fhh_gc_cot_host(fhh_ctx* ctx, uint64_t n, uint32_t bits, const uint8_t* gb_b
  * message), rows 1 .. 2^b - 1 send lo64(hash) ^ pair[o_r]. Outputs: msgs [n][2^bits - 1] u64 (may be
  * NULL), gb_share / ev_share [n] (r1 and the evaluator's value: gb - ev = eq mod p), ev_zero /
  * ev_active [n][bits][16] (may be NULL). Garbler 2^b AES per test, evaluator 1. The labels OT's index
- * is k npad + i with npad = n rounded up to 64 (b = 3, 4) or, since r06, to 512 (b <= 2: the table kernels
- * read the OT's tile-major matrices, whose 512-OT tiles must hold one client range per bit). */
+ * is k npad + i with npad = n rounded up to 64 (b = 3, 4) or to 512 (b <= 2). The table kernels read the OT's
+ * tile-major matrices at every b <= 4: at b <= 2 a 512-OT tile holds one client range per bit, at b = 3, 4 a
+ * bit's 512-test window starts at any even word of a tile (fhh_set_table_row_major: the row-major labels). */
 int fhh_gt_cot_host(fhh_ctx* ctx, uint64_t n, uint32_t bits, const uint8_t* gb_bits, const uint8_t* ev_bits,
                     uint32_t mask, uint64_t gate_base, const uint8_t base_seeds[128 * 2 * 16],
                     const uint8_t base_choice[16], uint64_t ctr_off, uint8_t* ev_zero, uint8_t* ev_active,
                     uint64_t* msgs, uint64_t* gb_share, uint64_t* ev_share);
-/* r06: the same table with its shares in Z_2^32 (bits <= 4; the party ABI's form 2, and at bits <= 2
+/* r06: the same table with its shares in Z_2^32 (bits <= 4; the party ABI's form 2 and
  * fhh_sim_config.table_ring32's form): row 0's value is lo32 of its hash, pair = (v, v +- 1 mod 2^32), rows
  * 1 .. 2^b - 1 send lo32(hash) ^ pair[o_r] (4 B); msgs / gb_share / ev_share as above, each value zero-extended
- * to u64 (gb - ev = eq mod 2^32). bits <= 2 on the tile-major kernels, bits = 3, 4 on the row-major
- * k_gt_garble_r32 / k_gt_eval_r32 (u32 messages and node values on the device). Oracle: orc_gt_garble_ring32 /
- * orc_gt_eval_ring32. */
+ * to u64 (gb - ev = eq mod 2^32). bits <= 4 on the tile-major kernels (bits = 3, 4 with nw = ceil(n / 64): the
+ * OT index and the labels are those of the row-major form); with fhh_set_table_row_major, bits = 3, 4 on the
+ * row-major k_gt_garble_r32 / k_gt_eval_r32 (u32 messages and node values on the device).
+ * Oracle: orc_gt_garble_ring32 / orc_gt_eval_ring32. */
 int fhh_gt_cot_ring32_host(fhh_ctx* ctx, uint64_t n, uint32_t bits, const uint8_t* gb_bits, const uint8_t* ev_bits,
                            uint32_t mask, uint64_t gate_base, const uint8_t base_seeds[128 * 2 * 16],
                            const uint8_t base_choice[16], uint64_t ctr_off, uint8_t* ev_zero, uint8_t* ev_active,
@@ -762,6 +764,14 @@ int fhh_variant_info(int variant, char* name, size_t cap, int* threads, int* gri
  * Applies to every later launch of the ctx (a pair launch and the device loop take the first ctx's).
  * fhh_set_variant recomputes the grid and so drops the override: set the variant first. */
 int fhh_set_expand_grid(fhh_ctx* ctx, int blocks);
+/* Test / diagnostic ABI, not a product knob: on = 1 makes the level loop and fhh_gt_cot*_host run the garbled
+ * tables of b = 3, 4 bits (d = 2) on the row-major labels: k_ot_rows_out's 16-B label per OT, k_gt_garble /
+ * k_gt_eval (Z_2^32: k_gt_garble_r32 / k_gt_eval_r32) with stored node values and a separate sums pass.
+ * on = 0, the default, runs the tile-major kernels, which read the labels OT's Q / T themselves and add the
+ * node values per child. Every output is the same either way; the row-major form is the A/B partner
+ * (tools/gt_tm_ab.py). No effect at b <= 2. The party ABI (fhh_gb_* / fhh_ev_*) keeps the row-major labels at
+ * b = 3, 4 whatever the flag says. The device loop follows the first ctx. FHH_E_ARG unless on is 0 or 1. */
+int fhh_set_table_row_major(fhh_ctx* ctx, int on);
 /* Test / diagnostic ABI, pure host arithmetic (no GPU): the work decomposition k_expand variant
  * `variant` gets on a grid of grid_blocks workgroups for a launch of njobs (<= 8) jobs with n_live[k]
  * live entries each over nw 64-client words — the same function the host launches and the device loop's
