@@ -55,7 +55,7 @@ EXPORTS = [
     "fhh_gb_garble", "fhh_gb_ot_labels", "fhh_gb_ot_shares", "fhh_ev_ot_labels", "fhh_ev_evaluate", "fhh_ev_ot_shares",
     "fhh_party_node_sums", "fhh_party_bytes_sent", "fhh_gc_party_test_cfgs", "fhh_memcpy_device",
     "fhh_cot_extend_host", "fhh_cot_extend_ss_host", "fhh_gc_cot_host", "fhh_gt_cot_host", "fhh_gt_cot_ring32_host",
-    "fhh_shard_plan",
+    "fhh_shard_plan", "fhh_reserve_clients", "fhh_add_keys_bincode_append",
 ]
 
 
@@ -311,6 +311,8 @@ def lib():
         "fhh_add_keys": (i, [vp, u64, u8p, u8p, u8p, u8p]),
         "fhh_gen_keys_pair": (i, [vp, vp, u64, u8p, u8p, u8p]),
         "fhh_add_keys_bincode": (i, [vp, u8p, u64]),
+        "fhh_reserve_clients": (i, [vp, u64]),
+        "fhh_add_keys_bincode_append": (i, [vp, u8p, u64]),
         "fhh_num_clients": (i, [vp, u64p]),
         "fhh_export_keys": (i, [vp, u8p, u8p, u8p, u8p]),
         "fhh_tree_init": (i, [vp]),

@@ -114,6 +114,20 @@ class KeyCollection:
             np.ascontiguousarray(request, np.uint8)
         self._chk(lib().fhh_add_keys_bincode(self._h, ptr(buf), buf.size))
 
+    def reserve_clients(self, n: int):
+        """Size the device key layout for n clients before `add_keys_bincode_append`. Optional on one
+        GPU (a reservation of the final count saves the growth and compaction copies), required with
+        `devices` (the shards' client ranges depend on the total)."""
+        self._chk(lib().fhh_reserve_clients(self._h, n))
+
+    def add_keys_bincode_append(self, request: bytes):
+        """One `add_keys` RPC of the leader's stream of batches (leader.rs:391-415; the framing of
+        `add_keys_bincode`): its clients are appended after those the collection holds and decoded on
+        the GPU into their place. A malformed batch raises and leaves the collection as it was."""
+        buf = np.frombuffer(bytes(request), np.uint8) if not isinstance(request, np.ndarray) else \
+            np.ascontiguousarray(request, np.uint8)
+        self._chk(lib().fhh_add_keys_bincode_append(self._h, ptr(buf), buf.size))
+
     def num_clients(self) -> int:
         n = ctypes.c_uint64()
         self._chk(lib().fhh_num_clients(self._h, ctypes.byref(n)))

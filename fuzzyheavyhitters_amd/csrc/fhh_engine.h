@@ -53,6 +53,10 @@ struct DevBuf {
         return hipSuccess;
     }
     template <class T> T* as() const { return static_cast<T*>(p); }
+    void swap(DevBuf& o) {
+        std::swap(p, o.p);
+        std::swap(bytes, o.bytes);
+    }
 };
 
 struct PinnedBuf {
@@ -126,6 +130,11 @@ struct fhh_ctx {
     bool dev_keys = false;        // keys resident on the device (uploaded or generated)
 
     DevBuf cw_seed, cw_bits, root_seed, key_idx, valid;
+    // keys appended batch by batch (fhh_add_keys_bincode_append): until tree_init npad / nw are the layout's
+    // capacity (>= n, grown geometrically), then the exact stride as on every other path
+    bool appended = false;
+    uint64_t reserved = 0;        // fhh_reserve_clients (0: none)
+    DevBuf app_buf, app_err;      // a batch's payload and its error word, kept from call to call
     DimTable tab[kMaxDims];
 
     Phase phase = Phase::kNoInit;
@@ -217,6 +226,16 @@ int node_partials(fhh_ctx* ctx, const void* vals, uint32_t fmt, uint64_t ld, uin
 int node_sums_finish(fhh_ctx* ctx, const uint64_t* partials, uint32_t fmt, void* out_a, void* out_b);
 // the add_keys RPC payload's n client records (without the leading u64), decoded on the device
 int add_keys_bincode_records(fhh_ctx* ctx, uint64_t n, const uint8_t* recs);
+// fhh_reserve_clients / fhh_add_keys_bincode_append on a one-GPU ctx, in the steps a multi-device ctx drives
+// per shard: the state check, the decode of m records onto the clients [n, n + m) (the layout grown first if
+// need be; *herr = the kernels' malformed-field bits, the count not advanced), then commit (n += m) or
+// rollback (the lanes from n on in n's word zero again, as before the batch)
+int append_reserve(fhh_ctx* ctx, uint64_t capacity);
+int append_check_state(fhh_ctx* ctx);
+int append_decode(fhh_ctx* ctx, uint64_t m, const uint8_t* recs, uint32_t* herr);
+void append_commit(fhh_ctx* ctx, uint64_t m);
+int append_rollback(fhh_ctx* ctx);
+std::string bincode_malformed_text(uint32_t herr);
 bool fmt_is_fe255(uint32_t fmt);
 
 // ---- fhh_group.cpp (multi-device ctx) --------------------------------------------------------
@@ -224,6 +243,9 @@ void group_destroy(fhh_ctx* g);
 int group_reset(fhh_ctx* g);
 int group_set_client_base(fhh_ctx* g, uint64_t base);
 int group_add_keys_bincode(fhh_ctx* g, const uint8_t* req, uint64_t len);
+int group_reserve_clients(fhh_ctx* g, uint64_t capacity);
+int group_add_keys_bincode_append(fhh_ctx* g, const uint8_t* req, uint64_t len);
+bool group_appended(const fhh_ctx* g);
 int group_gen_keys_pair(fhh_ctx* g0, fhh_ctx* g1, uint64_t n, const uint8_t* left, const uint8_t* right,
                         const uint8_t* roots);
 int group_num_clients(const fhh_ctx* g, uint64_t* n);

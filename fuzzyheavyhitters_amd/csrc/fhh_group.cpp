@@ -90,6 +90,10 @@ struct Group {
     std::vector<int> devices;
     std::vector<uint64_t> base, count;       // client range per shard (after placement)
     bool placed = false;                     // keys live on the shards
+    // appended batches (fhh_add_keys_bincode_append): the reservation fixes base / count, the shards fill in
+    // client order, app_n clients so far
+    uint64_t reserved = 0, app_n = 0;
+    bool appended = false;
     uint64_t client_base = 0;                // fhh_set_client_base of the collection
     bool distinct = false;                   // every shard on its own GPU
     bool force_host = false;                 // FHH_GROUP_REDUCE=host
@@ -190,6 +194,8 @@ int group_reset(fhh_ctx* g) {
         if (rc) return g->fail(rc, s->err);
     }
     G.placed = false;
+    G.appended = false;
+    G.reserved = G.app_n = 0;
     g->h_key_idx.clear();
     g->h_root.clear();
     g->h_cws.clear();
@@ -216,6 +222,7 @@ int group_add_keys_bincode(fhh_ctx* g, const uint8_t* req, uint64_t len) {
     if (n > (len - 8) / R || 8 + n * R != len)
         return g->fail(FHH_E_ARG, "add_keys_bincode: length does not match n clients x n_dims x data_len");
     plan(G, n);
+    G.reserved = 0;   // a one-shot placement replaces an unused reservation
     G.placed = true;
     // each shard uploads and decodes its own slice of the records (clients are fixed-size records)
     const int rc = fan_out(g, [&](size_t k, fhh_ctx* s) {
@@ -229,6 +236,92 @@ int group_add_keys_bincode(fhh_ctx* g, const uint8_t* req, uint64_t len) {
     return FHH_OK;
 }
 
+// fhh_reserve_clients on a multi-device ctx: placement needs the total up front, so the reservation fixes the
+// shards' client ranges (the plan of every other path) and sizes each shard's layout for its range — the
+// capacity stride is then the exact one and tree_init copies nothing.
+int group_reserve_clients(fhh_ctx* g, uint64_t capacity) {
+    Group& G = *g->group;
+    for (auto* s : G.shards)
+        if (s->phase != Phase::kNoInit) return g->fail(FHH_E_STATE, "reserve_clients: tree_init has run");
+    if (g->h_n || (G.placed && !G.appended))
+        return g->fail(FHH_E_STATE, "reserve_clients: ctx holds keys that were not appended");
+    if (capacity == 0 || capacity < G.app_n)
+        return g->fail(FHH_E_ARG, "reserve_clients: capacity below the current client count");
+    if (G.appended) {
+        if (capacity == G.reserved) return FHH_OK;
+        return g->fail(FHH_E_STATE, "reserve_clients: the shards' ranges were fixed by the reservation of " +
+                                        std::to_string(G.reserved) + " clients (fhh_reset first)");
+    }
+    plan(G, capacity);
+    for (size_t k = 0; k < G.shards.size(); k++) {
+        if (!G.count[k]) continue;
+        const int rc = append_reserve(G.shards[k], G.count[k]);
+        if (rc) return shard_fail(g, k, rc);
+    }
+    G.reserved = capacity;
+    G.app_n = 0;
+    return FHH_OK;
+}
+
+bool group_appended(const fhh_ctx* g) { return g->group->appended; }
+
+// One add_keys RPC on a multi-device ctx: routed by global client index. Records are fixed-size, so a batch
+// that straddles a shard boundary is cut by pointer arithmetic (as group_add_keys_bincode slices). Every
+// shard the batch touches decodes its slice first; the counts advance only if all of them accepted it,
+// otherwise each is rolled back. A batch touches one shard, seldom two: the slices run one after the other.
+int group_add_keys_bincode_append(fhh_ctx* g, const uint8_t* req, uint64_t len) {
+    Group& G = *g->group;
+    for (auto* s : G.shards)
+        if (s->phase != Phase::kNoInit)
+            return g->fail(FHH_E_STATE, "add_keys_bincode_append: tree_init has run (fhh_reset first)");
+    if (g->h_n) return g->fail(FHH_E_STATE, "add_keys_bincode_append: ctx holds keys staged by fhh_add_keys");
+    if (G.placed && !G.appended)
+        return g->fail(FHH_E_STATE, "add_keys_bincode_append: ctx holds keys of fhh_gen_keys_pair / fhh_add_keys_bincode");
+    if (!G.reserved)
+        return g->fail(FHH_E_STATE, "add_keys_bincode_append: a multi-device ctx needs fhh_reserve_clients(total) first "
+                                    "(the shards' client ranges depend on the total)");
+    if (!req || len < 8) return g->fail(FHH_E_ARG, "add_keys_bincode_append: buffer shorter than the u64 length");
+    uint64_t m = 0;
+    for (int i = 0; i < 8; i++) m |= (uint64_t)req[i] << (8 * i);
+    const uint64_t KB = 25 + 20ull * g->L, R = 8 + (uint64_t)g->K * KB;
+    if (m == 0) return g->fail(FHH_E_ARG, "add_keys_bincode_append: no clients");
+    if (m > (len - 8) / R || 8 + m * R != len)
+        return g->fail(FHH_E_ARG, "add_keys_bincode_append: length does not match n clients x n_dims x data_len");
+    if (m > G.reserved - G.app_n)
+        return g->fail(FHH_E_ARG, "add_keys_bincode_append: " + std::to_string(G.app_n) + " + " + std::to_string(m) +
+                                      " clients exceed the reservation of " + std::to_string(G.reserved));
+    const uint64_t c0 = G.app_n, c1 = c0 + m;
+    std::vector<size_t> hit;
+    std::vector<uint64_t> cnt;
+    uint32_t herr = 0;
+    int rc = FHH_OK;
+    size_t failed = 0;
+    for (size_t k = 0; k < G.shards.size() && !rc && !herr; k++) {
+        const uint64_t lo = std::max(c0, G.base[k]), hi = std::min(c1, G.base[k] + G.count[k]);
+        if (lo >= hi) continue;
+        fhh_ctx* s = G.shards[k];
+        if (s->n != lo - G.base[k]) return g->fail(FHH_E_STATE, "add_keys_bincode_append: shard " + std::to_string(k) + " out of step");
+        hit.push_back(k);
+        cnt.push_back(hi - lo);
+        uint32_t e = 0;
+        rc = append_decode(s, hi - lo, req + 8 + (lo - c0) * R, &e);
+        herr |= e;
+        failed = k;
+    }
+    if (rc || herr) {   // no shard advances; the words the slices shared with held clients are restored
+        for (size_t k : hit) (void)append_rollback(G.shards[k]);
+        if (rc) return shard_fail(g, failed, rc);
+        return g->fail(FHH_E_ARG, "add_keys_bincode_append: " + bincode_malformed_text(herr));
+    }
+    for (size_t i = 0; i < hit.size(); i++) append_commit(G.shards[hit[i]], cnt[i]);
+    G.app_n = c1;
+    if (!G.appended) {
+        G.appended = G.placed = true;
+        set_bases(G);
+    }
+    return FHH_OK;
+}
+
 int group_gen_keys_pair(fhh_ctx* g0, fhh_ctx* g1, uint64_t n, const uint8_t* left, const uint8_t* right,
                         const uint8_t* roots) {
     if (!g0->group || !g1->group) return g0->fail(FHH_E_ARG, "gen_keys_pair: both ctxs must be multi-device ctxs");
@@ -239,6 +332,7 @@ int group_gen_keys_pair(fhh_ctx* g0, fhh_ctx* g1, uint64_t n, const uint8_t* lef
     if (!left || !right || !roots) return g0->fail(FHH_E_ARG, "gen_keys_pair: NULL buffer");
     plan(G0, n);
     plan(G1, n);
+    G0.reserved = G1.reserved = 0;
     G0.placed = G1.placed = true;
     const size_t dL = (size_t)g0->d * g0->L, dR = (size_t)g0->d * 64;
     const int rc = fan_out(g0, [&](size_t k, fhh_ctx* s) {
@@ -258,7 +352,8 @@ int group_gen_keys_pair(fhh_ctx* g0, fhh_ctx* g1, uint64_t n, const uint8_t* lef
 int group_num_clients(const fhh_ctx* g, uint64_t* n) {
     const Group& G = *g->group;
     uint64_t v = g->h_n;
-    if (G.placed)
+    if (G.appended) v = G.app_n;   // the shards fill in client order up to their reserved ranges
+    else if (G.placed)
         for (uint64_t c : G.count) v += c;
     if (n) *n = v;
     return FHH_OK;
@@ -290,6 +385,7 @@ int group_tree_init(fhh_ctx* g) {
         const uint64_t n = g->h_n;
         const size_t K = g->K, L = g->L;
         plan(G, n);
+        G.reserved = 0;
         G.placed = true;
         int rc = fan_out(g, [&](size_t k, fhh_ctx* s) {
             const size_t b = G.base[k];
@@ -314,6 +410,9 @@ int group_tree_init(fhh_ctx* g) {
         set_bases(G);
     }
     if (!G.placed) return g->fail(FHH_E_STATE, "tree_init with no keys (collect.rs:83)");
+    if (G.appended && G.app_n != G.reserved)
+        return g->fail(FHH_E_STATE, "tree_init: " + std::to_string(G.app_n) + " clients appended of the " +
+                                        std::to_string(G.reserved) + " reserved (the shards' ranges are fixed by the reservation)");
     int rc = fan_out(g, [&](size_t, fhh_ctx* s) { return fhh_tree_init(s); });
     if (rc) return rc;
     return ensure_comms(g);

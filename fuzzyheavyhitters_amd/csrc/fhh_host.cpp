@@ -149,6 +149,8 @@ bool fe255_ge_u32(const std::array<uint32_t, 8>& v, uint32_t t) { return fhh::fe
 
 // ---- device key / table management -----------------------------------------------------------
 int alloc_keys(fhh_ctx* ctx, uint64_t n) {
+    ctx->appended = false;   // a one-shot layout replaces an unused reservation
+    ctx->reserved = 0;
     ctx->n = n;
     ctx->nw = (n + 63) / 64;
     if (ctx->nw == 0) ctx->nw = 1;
@@ -661,6 +663,138 @@ int add_keys_bincode_records(fhh_ctx* ctx, uint64_t n, const uint8_t* recs) {
     }
     ctx->dev_keys = true;
     return FHH_OK;
+}
+
+// ---- appended batches (fhh_reserve_clients / fhh_add_keys_bincode_append) ----------------------
+std::string bincode_malformed_text(uint32_t herr) {
+    return std::string("malformed request (") + ((herr & 1) ? "bool byte > 1 " : "") +
+           ((herr & 2) ? "cor_words length " : "") + ((herr & 4) ? "dims per client" : "") + ")";
+}
+
+// The key buffers at a row stride of new_npad clients (a multiple of 64): the rows are [row][npad], so the
+// clients held so far are copied row by row into fresh buffers (old and new are both live until the copy is
+// done); an empty layout only grows its allocations.
+static int relayout_keys(fhh_ctx* ctx, uint64_t new_npad) {
+    const size_t K = ctx->K, L = ctx->L, new_nw = new_npad / 64;
+    if (new_npad == ctx->npad) return FHH_OK;
+    if (new_npad >> 32) return ctx->fail(FHH_E_ARG, "add_keys: more than 2^32 clients on one GPU");
+    const uint64_t used_w = (ctx->n + 63) / 64;   // <= new_nw
+    if (ctx->n == 0) {
+        HIP_TRY(ctx, ctx->cw_seed.ensure(L * K * new_npad * 16));
+        HIP_TRY(ctx, ctx->cw_bits.ensure(L * K * 4 * new_nw * 8));
+        HIP_TRY(ctx, ctx->root_seed.ensure(K * new_npad * 16));
+        HIP_TRY(ctx, ctx->key_idx.ensure(K * new_nw * 8));
+    } else {
+        DevBuf cs, cb, rs, ki;
+        HIP_TRY(ctx, cs.ensure(L * K * new_npad * 16));
+        HIP_TRY(ctx, cb.ensure(L * K * 4 * new_nw * 8));
+        HIP_TRY(ctx, rs.ensure(K * new_npad * 16));
+        HIP_TRY(ctx, ki.ensure(K * new_nw * 8));
+        HIP_TRY(ctx, launch_repitch_seeds(ctx->cw_seed.as<uint4>(), cs.as<uint4>(), L * K, used_w * 64, ctx->npad,
+                                          new_npad, ctx->stream));
+        HIP_TRY(ctx, launch_repitch_words(ctx->cw_bits.as<uint64_t>(), cb.as<uint64_t>(), L * K * 4, used_w, ctx->nw,
+                                          new_nw, ctx->stream));
+        HIP_TRY(ctx, launch_repitch_seeds(ctx->root_seed.as<uint4>(), rs.as<uint4>(), K, used_w * 64, ctx->npad,
+                                          new_npad, ctx->stream));
+        HIP_TRY(ctx, launch_repitch_words(ctx->key_idx.as<uint64_t>(), ki.as<uint64_t>(), K, used_w, ctx->nw, new_nw,
+                                          ctx->stream));
+        int rc = sync(ctx);
+        if (rc) return rc;
+        ctx->cw_seed.swap(cs);
+        ctx->cw_bits.swap(cb);
+        ctx->root_seed.swap(rs);
+        ctx->key_idx.swap(ki);
+    }
+    ctx->npad = new_npad;
+    ctx->nw = new_nw;
+    return FHH_OK;
+}
+
+int append_check_state(fhh_ctx* ctx) {
+    if (ctx->phase != Phase::kNoInit)
+        return ctx->fail(FHH_E_STATE, "add_keys_bincode_append: tree_init has run (fhh_reset first: the prefix tables are sized by the client count)");
+    if (ctx->h_n) return ctx->fail(FHH_E_STATE, "add_keys_bincode_append: ctx holds keys staged by fhh_add_keys");
+    if (ctx->dev_keys && !ctx->appended)
+        return ctx->fail(FHH_E_STATE, "add_keys_bincode_append: ctx holds keys of fhh_gen_keys_pair / fhh_add_keys_bincode");
+    return FHH_OK;
+}
+
+int append_reserve(fhh_ctx* ctx, uint64_t capacity) {
+    int rc = set_device(ctx);
+    if (rc) return rc;
+    if (ctx->phase != Phase::kNoInit) return ctx->fail(FHH_E_STATE, "reserve_clients: tree_init has run");
+    if (ctx->h_n || (ctx->dev_keys && !ctx->appended))
+        return ctx->fail(FHH_E_STATE, "reserve_clients: ctx holds keys that were not appended");
+    if (capacity == 0 || capacity < ctx->n)
+        return ctx->fail(FHH_E_ARG, "reserve_clients: capacity below the current client count");
+    const uint64_t npad = (capacity + 63) / 64 * 64;
+    if (!ctx->appended) ctx->n = ctx->npad = ctx->nw = 0;   // an empty ctx: no layout yet
+    if (npad > ctx->npad) {
+        rc = relayout_keys(ctx, npad);
+        if (rc) return rc;
+    }
+    ctx->reserved = capacity;
+    return FHH_OK;
+}
+
+int append_decode(fhh_ctx* ctx, uint64_t m, const uint8_t* recs, uint32_t* herr) {
+    int rc = set_device(ctx);
+    if (rc) return rc;
+    rc = append_check_state(ctx);
+    if (rc) return rc;
+    if (!ctx->appended && !ctx->reserved) ctx->n = ctx->npad = ctx->nw = 0;
+    const uint64_t c0 = ctx->n, need = (c0 + m + 63) / 64 * 64;
+    if (need > ctx->npad) {   // geometric growth: a pitch-changing copy of every buffer
+        rc = relayout_keys(ctx, std::max(need, 2 * ctx->npad));
+        if (rc == FHH_E_NOMEM && need < 2 * ctx->npad) {   // the doubling does not fit: exactly what is needed
+            (void)hipGetLastError();
+            rc = relayout_keys(ctx, need);
+        }
+        if (rc) return rc;
+    }
+    const uint64_t KB = 25 + 20ull * ctx->L, R = 8 + (uint64_t)ctx->K * KB;
+    HIP_TRY(ctx, ctx->app_buf.ensure(8 + m * R + 4));   // whole-dword reads: up to 3 B past the end
+    HIP_TRY(ctx, ctx->app_err.ensure(4));
+    HIP_TRY(ctx, hipMemsetAsync(ctx->app_err.p, 0, 4, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->app_buf.p, &m, 8, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->app_buf.as<uint8_t>() + 8, recs, m * R, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, launch_keys_from_bincode_at(ctx->app_buf.as<uint8_t>(), c0, m, ctx->d, ctx->L, (uint32_t)ctx->npad,
+                                             (uint32_t)ctx->nw, ctx->cw_seed.as<uint4>(), ctx->cw_bits.as<uint64_t>(),
+                                             ctx->root_seed.as<uint4>(), ctx->key_idx.as<uint64_t>(),
+                                             ctx->app_err.as<uint32_t>(), ctx->stream));
+    *herr = 0;
+    HIP_TRY(ctx, hipMemcpyAsync(herr, ctx->app_err.p, 4, hipMemcpyDeviceToHost, ctx->stream));
+    return sync(ctx);
+}
+
+void append_commit(fhh_ctx* ctx, uint64_t m) {
+    ctx->n += m;
+    ctx->dev_keys = true;
+    ctx->appended = true;
+}
+
+int append_rollback(fhh_ctx* ctx) {
+    if ((ctx->n & 63) == 0) return FHH_OK;   // the refused batch shared no word with the clients held
+    int rc = set_device(ctx);
+    if (rc) return rc;
+    HIP_TRY(ctx, launch_keys_from_bincode_at(ctx->app_buf.as<uint8_t>(), ctx->n, 0, ctx->d, ctx->L, (uint32_t)ctx->npad,
+                                             (uint32_t)ctx->nw, ctx->cw_seed.as<uint4>(), ctx->cw_bits.as<uint64_t>(),
+                                             ctx->root_seed.as<uint4>(), ctx->key_idx.as<uint64_t>(),
+                                             ctx->app_err.as<uint32_t>(), ctx->stream));
+    return sync(ctx);
+}
+
+// tree_init on appended keys: the capacity stride becomes the exact one (64 ceil(n / 64), one compacting
+// copy unless the capacity already is that) and `valid` is built, so every buffer is what alloc_keys + one
+// decode of the whole population leave
+static int finish_appended(fhh_ctx* ctx) {
+    int rc = relayout_keys(ctx, (ctx->n + 63) / 64 * 64);
+    if (rc) return rc;
+    HIP_TRY(ctx, ctx->valid.ensure(ctx->nw * 8));
+    std::vector<uint64_t> v(ctx->nw, ~0ull);
+    if (ctx->n % 64) v[ctx->nw - 1] = (1ull << (ctx->n % 64)) - 1;
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->valid.p, v.data(), ctx->nw * 8, hipMemcpyHostToDevice, ctx->stream));
+    return sync(ctx);
 }
 }  // namespace eng
 }  // namespace fhh
@@ -1776,6 +1910,8 @@ int fhh_reset(fhh_ctx* ctx) {
     ctx->h_cwb.clear();
     ctx->h_n = 0;
     ctx->dev_keys = false;
+    ctx->appended = false;
+    ctx->reserved = 0;
     ctx->n = ctx->npad = ctx->nw = 0;
     ctx->phase = Phase::kNoInit;
     ctx->frontier.clear();
@@ -1785,7 +1921,12 @@ int fhh_reset(fhh_ctx* ctx) {
     ctx->last_hist.clear();
     ctx->pending_C = 0;
     ctx->level = 0;
-    for (auto& T : ctx->tab) T.live.clear();
+    for (auto& T : ctx->tab) {
+        T.live.clear();
+        // entries are sized by npad: the next collection may be larger, so its tables are sized afresh (the
+        // allocations themselves are kept and reused where they are large enough)
+        T.cap[0] = T.cap[1] = 0;
+    }
     return FHH_OK;
 }
 
@@ -1802,6 +1943,7 @@ int fhh_add_keys(fhh_ctx* ctx, uint64_t n, const uint8_t* key_idx, const uint8_t
     if (n == 0) return FHH_OK;
     if (!key_idx || !root_seed || !cw_seed || !cw_bits) return ctx->fail(FHH_E_ARG, "add_keys: NULL buffer");
     if (ctx->dev_keys) return ctx->fail(FHH_E_STATE, "add_keys after keys were placed on the device");
+    if (ctx->group && group_appended(ctx)) return ctx->fail(FHH_E_STATE, "add_keys onto appended keys");
     const size_t K = ctx->K, L = ctx->L;
     ctx->h_key_idx.insert(ctx->h_key_idx.end(), key_idx, key_idx + n * K);
     ctx->h_root.insert(ctx->h_root.end(), root_seed, root_seed + n * K * 16);
@@ -1934,6 +2076,36 @@ int fhh_add_keys_bincode(fhh_ctx* ctx, const uint8_t* req, uint64_t len) {
     return add_keys_bincode_records(ctx, n, req + 8);
 }
 
+int fhh_reserve_clients(fhh_ctx* ctx, uint64_t capacity) {
+    CTX_CHECK(ctx);
+    if (ctx->group) return group_reserve_clients(ctx, capacity);
+    return append_reserve(ctx, capacity);
+}
+
+int fhh_add_keys_bincode_append(fhh_ctx* ctx, const uint8_t* req, uint64_t len) {
+    CTX_CHECK(ctx);
+    if (ctx->group) return group_add_keys_bincode_append(ctx, req, len);
+    int rc = append_check_state(ctx);
+    if (rc) return rc;
+    if (!req || len < 8) return ctx->fail(FHH_E_ARG, "add_keys_bincode_append: buffer shorter than the u64 length");
+    uint64_t m = 0;
+    for (int i = 0; i < 8; i++) m |= (uint64_t)req[i] << (8 * i);
+    const uint64_t KB = 25 + 20ull * ctx->L, R = 8 + (uint64_t)ctx->K * KB;
+    if (m == 0) return ctx->fail(FHH_E_ARG, "add_keys_bincode_append: no clients");
+    if (m > (len - 8) / R || 8 + m * R != len)
+        return ctx->fail(FHH_E_ARG, "add_keys_bincode_append: length does not match n clients x n_dims x data_len");
+    uint32_t herr = 0;
+    rc = append_decode(ctx, m, req + 8, &herr);
+    if (rc) return rc;
+    if (herr) {
+        rc = append_rollback(ctx);
+        if (rc) return rc;
+        return ctx->fail(FHH_E_ARG, "add_keys_bincode_append: " + bincode_malformed_text(herr));
+    }
+    append_commit(ctx, m);
+    return FHH_OK;
+}
+
 int fhh_tree_init(fhh_ctx* ctx) {
     CTX_CHECK(ctx);
     if (ctx->group) return group_tree_init(ctx);
@@ -1942,6 +2114,10 @@ int fhh_tree_init(fhh_ctx* ctx) {
     rc = upload_staged_keys(ctx);
     if (rc) return rc;
     if (!ctx->dev_keys || ctx->n == 0) return ctx->fail(FHH_E_STATE, "tree_init with no keys (collect.rs:83)");
+    if (ctx->appended) {
+        rc = finish_appended(ctx);
+        if (rc) return rc;
+    }
     for (uint32_t j = 0; j < ctx->d; j++) {
         DimTable& T = ctx->tab[j];
         T.cur = 0;

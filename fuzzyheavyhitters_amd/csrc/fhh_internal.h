@@ -329,6 +329,17 @@ hipError_t launch_keys_from_aos(const uint8_t* key_idx, const uint8_t* root_seed
 hipError_t launch_keys_from_bincode(const uint8_t* buf, uint64_t n, uint32_t d, uint32_t L, uint32_t npad, uint32_t nw,
                                     uint4* d_cw_seed, uint64_t* d_cw_bits, uint4* d_root, uint64_t* d_key_idx,
                                     uint32_t* err, hipStream_t stream);
+// an appended batch: the m records of buf onto the clients [c0, c0 + m) of a layout of nw >= ceil((c0 + m) / 64)
+// words (bincode_span.h); m = 0 re-zeroes the lanes from c0 on in c0's word
+hipError_t launch_keys_from_bincode_at(const uint8_t* buf, uint64_t c0, uint64_t m, uint32_t d, uint32_t L,
+                                       uint32_t npad, uint32_t nw, uint4* d_cw_seed, uint64_t* d_cw_bits, uint4* d_root,
+                                       uint64_t* d_key_idx, uint32_t* err, hipStream_t stream);
+// `rows` rows of `width` elements from row pitch src_pitch to dst_pitch (elements): a change of the key
+// layout's capacity
+hipError_t launch_repitch_seeds(const uint4* src, uint4* dst, uint64_t rows, uint64_t width, uint64_t src_pitch,
+                                uint64_t dst_pitch, hipStream_t stream);
+hipError_t launch_repitch_words(const uint64_t* src, uint64_t* dst, uint64_t rows, uint64_t width, uint64_t src_pitch,
+                                uint64_t dst_pitch, hipStream_t stream);
 // occupancy-derived persistent grid for k_expand variant on `device`
 int expand_grid(int device, int variant);
 // RCCL all-reduce (sum, u64) on `stream` (fhh_comm.cpp); asynchronous

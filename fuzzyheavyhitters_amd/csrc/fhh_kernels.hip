@@ -15,6 +15,7 @@
 //   k_keys_from_aos add_key wire layout -> SoA device layout
 #include "fhh_internal.h"
 #include "expand_kernel.h"
+#include "bincode_span.h"
 #include "../../include/fhh.h"
 // The measured-negative k_expand forms of r01-r03 (bitsliced VALU AES, the T-table + pair-sliced
 // hybrid, the earlier T-table variants) and their generated AES programs were removed in r06; they are
@@ -1013,6 +1014,190 @@ hipError_t launch_keys_from_bincode(const uint8_t* buf, uint64_t n, uint32_t d, 
     hipLaunchKernelGGL(k_keys_from_bincode, dim3((unsigned)blocks), dim3(256), 0, stream, buf, n, d, L, npad, nw,
                        d_cw_seed, d_cw_bits, d_root, d_key_idx, err, L);
     return hipGetLastError();
+}
+
+// ---- appended add_keys batches (fhh_add_keys_bincode_append) -------------------------------------
+// The two decode kernels above with a destination offset: record i of the batch (m records in buf, after its
+// u64 count) lands on client c0 + i of a layout that already holds the clients below c0, so the word is
+// floor((c0 + i) / 64), the lane (c0 + i) mod 64, and the batch's first and last words may be shared with
+// other clients (bincode_span.h gives each word's lanes, source record and tail). Seed stores are predicated
+// on the word's lanes + tail (the tail, the lanes after the batch's end in its last word, is written as zero:
+// the layout's lanes past n stay zero and the next batch overwrites them); a bit-plane word is merged as
+// (old & ~mask) | (ballot & mask) by one lane — one tile owns a (row, word) per launch and launches on the
+// ctx stream are ordered. The one-shot kernels are left as they are (their code and resource use unchanged).
+__global__ __launch_bounds__(256) void k_bincode_cw_tiles_at(const uint8_t* buf, uint64_t c0, uint64_t m, uint32_t d,
+                                                             uint32_t L, uint32_t npad, uint32_t nw, uint4* d_cw_seed,
+                                                             uint64_t* d_cw_bits, uint32_t* err) {
+    __shared__ uint32_t st[64 * kBcRow];
+    const uint32_t K = 2 * d;
+    const uint64_t KB = 25 + 20ull * L, R = 8 + (uint64_t)K * KB;
+    const uint32_t nlb = (L + kBcLevels - 1) / kBcLevels;
+    const uint64_t nwb = bc_span_words(c0, m), w0 = bc_span_first_word(c0);
+    const uint64_t tiles = nwb * K * nlb;
+    const uint32_t lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    for (uint64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+        const uint64_t j = tile % nwb;
+        const uint32_t kk = (uint32_t)((tile / nwb) % K);
+        const uint32_t l0 = (uint32_t)(tile / (nwb * K)) * kBcLevels;
+        const uint32_t nl = min((uint32_t)kBcLevels, L - l0);
+        const BcWord sp = bc_span_word(c0, m, j);
+        const uint64_t w = w0 + j;
+        // stage (as k_bincode_cw_tiles): wave wv takes the word's lanes wv + 4 i, each from its own record
+        uint32_t v[16][3];
+#pragma unroll
+        for (int i = 0; i < 16; i++) {
+            const uint32_t ln = wv + 4 * i;
+            const bool in = (sp.lanes >> ln) & 1;
+            const uint64_t rec = in ? (uint64_t)(sp.src0 + (int64_t)ln) : 0;
+            const uint64_t s0 = 8 + rec * R + 8 + kk * KB + 25 + 20ull * l0;   // level l0's CorWord
+            const uint64_t a0 = s0 & ~3ull;
+            const uint32_t ndw = in ? (uint32_t)((s0 + 20ull * nl + 3 - a0) / 4) : 0u;   // <= kBcRow
+            const uint32_t* src = reinterpret_cast<const uint32_t*>(buf + a0);
+#pragma unroll
+            for (int r = 0; r < 3; r++) {
+                const uint32_t q = lane + 64 * r;
+                v[i][r] = q < ndw ? src[q] : 0u;
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < 16; i++)
+#pragma unroll
+            for (int r = 0; r < 3; r++) {
+                const uint32_t q = lane + 64 * r;
+                if (q < (uint32_t)kBcRow) st[(wv + 4 * i) * kBcRow + q] = v[i][r];
+            }
+        __syncthreads();
+        const uint64_t c = w * 64 + lane;
+        const bool in = (sp.lanes >> lane) & 1;
+        const uint64_t mask = sp.lanes | sp.tail;
+        const bool wr = (mask >> lane) & 1;
+        const uint64_t rec = in ? (uint64_t)(sp.src0 + (int64_t)lane) : 0;
+        const uint32_t sh = (uint32_t)((8 + rec * R + 8 + kk * KB + 25 + 20ull * l0) & 3) * 8;
+        uint32_t bad = 0;
+        for (uint32_t li = wv; li < nl; li += 4) {
+            uint4 val = make_uint4(0, 0, 0, 0);
+            uint32_t nib = 0;
+            if (in) {
+                const uint32_t* row = st + lane * kBcRow + 5 * li;   // 5 li + 5 < kBcRow
+                uint32_t u[5];
+#pragma unroll
+                for (int k = 0; k < 5; k++) u[k] = __builtin_amdgcn_alignbit(row[k + 1], row[k], sh);
+                val = make_uint4(u[0], u[1], u[2], u[3]);
+#pragma unroll
+                for (int b = 0; b < 4; b++) {
+                    const uint32_t x = (u[4] >> (8 * b)) & 0xFFu;
+                    bad |= x > 1 ? 1u : 0u;
+                    nib |= (x & 1u) << b;
+                }
+            }
+            const size_t rowi = (size_t)(l0 + li) * K + kk;
+            if (wr) d_cw_seed[rowi * npad + c] = val;
+            uint64_t q[4];
+#pragma unroll
+            for (int b = 0; b < 4; b++) q[b] = __ballot((nib >> b) & 1);
+            if (lane == 0)
+#pragma unroll
+                for (int b = 0; b < 4; b++) {
+                    uint64_t* p = d_cw_bits + (rowi * 4 + b) * nw + w;
+                    *p = ~mask ? ((*p & ~mask) | (q[b] & mask)) : q[b];
+                }
+        }
+        if (bad) atomicOr(err, bad);
+        __syncthreads();
+    }
+}
+
+// level L of an appended batch: roots, key_idx and the records' length fields, one wave per (key, word)
+__global__ void k_keys_from_bincode_at(const uint8_t* buf, uint64_t c0, uint64_t m, uint32_t d, uint32_t L,
+                                       uint32_t npad, uint32_t nw, uint4* d_root, uint64_t* d_key_idx, uint32_t* err) {
+    const uint32_t K = 2 * d;
+    const uint64_t KB = 25 + 20ull * L, R = 8 + (uint64_t)K * KB;
+    const uint32_t lane = threadIdx.x & 63;
+    const uint64_t wpb = blockDim.x >> 6;
+    const uint64_t nwaves = (uint64_t)gridDim.x * wpb;
+    const uint64_t nwb = bc_span_words(c0, m), w0 = bc_span_first_word(c0);
+    const uint64_t items = nwb * K;
+    for (uint64_t item = (uint64_t)blockIdx.x * wpb + wave_id_uniform(); item < items; item += nwaves) {
+        const uint64_t j = item % nwb;
+        const uint32_t kk = (uint32_t)(item / nwb);
+        const BcWord sp = bc_span_word(c0, m, j);
+        const uint64_t w = w0 + j, mask = sp.lanes | sp.tail;
+        uint4 v = make_uint4(0, 0, 0, 0);
+        uint32_t ki = 0, bad = 0;
+        if ((sp.lanes >> lane) & 1) {
+            const uint8_t* rec = buf + 8 + (uint64_t)(sp.src0 + (int64_t)lane) * R;
+            const uint8_t* key = rec + 8 + (uint64_t)kk * KB;
+            ki = key[0];
+            bad |= ki > 1 ? 1u : 0u;
+            v = load_seed(key + 1);
+            bad |= load_u64_le(key + 17) != L ? 2u : 0u;
+            if (kk == 0) bad |= load_u64_le(rec) != d ? 4u : 0u;
+        }
+        if ((mask >> lane) & 1) d_root[(size_t)kk * npad + w * 64 + lane] = v;
+        const uint64_t q = __ballot(ki & 1u);
+        if (lane == 0) {
+            uint64_t* p = d_key_idx + (size_t)kk * nw + w;
+            *p = ~mask ? ((*p & ~mask) | (q & mask)) : q;
+        }
+        if (bad) atomicOr(err, bad);
+    }
+}
+
+hipError_t launch_keys_from_bincode_at(const uint8_t* buf, uint64_t c0, uint64_t m, uint32_t d, uint32_t L,
+                                       uint32_t npad, uint32_t nw, uint4* d_cw_seed, uint64_t* d_cw_bits, uint4* d_root,
+                                       uint64_t* d_key_idx, uint32_t* err, hipStream_t stream) {
+    const uint64_t nwb = bc_span_words(c0, m);
+    if (nwb == 0) return hipSuccess;
+    if (bc_span_first_word(c0) + nwb > nw) return hipErrorInvalidValue;   // the caller sizes the layout first
+    int dev = 0, cus = 256;
+    (void)hipGetDevice(&dev);
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
+    const uint64_t tiles = nwb * 2 * d * ((L + kBcLevels - 1) / kBcLevels);
+    if (tiles) {
+        const uint64_t cap = (uint64_t)cus * 8;
+        hipLaunchKernelGGL(k_bincode_cw_tiles_at, dim3((unsigned)(tiles < cap ? tiles : cap)), dim3(256), 0, stream, buf,
+                           c0, m, d, L, npad, nw, d_cw_seed, d_cw_bits, err);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    uint64_t blocks = (nwb * 2 * d + 3) / 4;
+    if (blocks > 8192) blocks = 8192;
+    hipLaunchKernelGGL(k_keys_from_bincode_at, dim3((unsigned)blocks), dim3(256), 0, stream, buf, c0, m, d, L, npad, nw,
+                       d_root, d_key_idx, err);
+    return hipGetLastError();
+}
+
+// rows of `width` elements from a layout of row pitch src_pitch into one of dst_pitch (elements): the key
+// buffers' rows are [row][npad], so a change of capacity changes every row's pitch
+template <class T>
+__global__ void k_repitch(const T* src, T* dst, uint64_t rows, uint64_t width, uint64_t src_pitch, uint64_t dst_pitch) {
+    const uint64_t total = rows * width;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (uint64_t)gridDim.x * blockDim.x) {
+        const uint64_t r = i / width, x = i % width;
+        dst[r * dst_pitch + x] = src[r * src_pitch + x];
+    }
+}
+
+template <class T>
+static hipError_t launch_repitch(const T* src, T* dst, uint64_t rows, uint64_t width, uint64_t src_pitch,
+                                 uint64_t dst_pitch, hipStream_t stream) {
+    const uint64_t total = rows * width;
+    if (total == 0) return hipSuccess;
+    uint64_t blocks = (total + 255) / 256;
+    if (blocks > 16384) blocks = 16384;
+    hipLaunchKernelGGL(k_repitch<T>, dim3((unsigned)blocks), dim3(256), 0, stream, src, dst, rows, width, src_pitch,
+                       dst_pitch);
+    return hipGetLastError();
+}
+
+hipError_t launch_repitch_seeds(const uint4* src, uint4* dst, uint64_t rows, uint64_t width, uint64_t src_pitch,
+                                uint64_t dst_pitch, hipStream_t stream) {
+    return launch_repitch(src, dst, rows, width, src_pitch, dst_pitch, stream);
+}
+
+hipError_t launch_repitch_words(const uint64_t* src, uint64_t* dst, uint64_t rows, uint64_t width, uint64_t src_pitch,
+                                uint64_t dst_pitch, hipStream_t stream) {
+    return launch_repitch(src, dst, rows, width, src_pitch, dst_pitch, stream);
 }
 
 hipError_t launch_keys_from_aos(const uint8_t* key_idx, const uint8_t* root_seed, const uint8_t* cw_seed,

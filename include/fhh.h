@@ -89,6 +89,28 @@ int fhh_add_keys(fhh_ctx* ctx, uint64_t n, const uint8_t* key_idx, const uint8_t
  * decode fails the request). */
 int fhh_add_keys_bincode(fhh_ctx* ctx, const uint8_t* req, uint64_t len);
 
+/* The leader's `add_keys` RPCs as they arrive: batches of addkey_batch_size clients, many in flight
+ * (leader.rs:391-415), each pushed onto the collection by the handler (server.rs:71-77).
+ * fhh_add_keys_bincode_append takes one such request (the framing of fhh_add_keys_bincode: u64 m, then m
+ * client records), appends its clients after those the ctx holds and decodes them on the GPU into their
+ * place in the device layout; it returns after the batch is decoded and checked. After batches b_0 .. b_k
+ * the ctx holds their clients in arrival order, and from fhh_tree_init on the device key buffers are those
+ * one fhh_add_keys_bincode call of the concatenated population leaves. A malformed batch (the errors of
+ * fhh_add_keys_bincode) returns FHH_E_ARG and leaves the collection as it was: the count does not advance
+ * and the next batch lands on the same clients. FHH_E_STATE if the ctx holds keys of fhh_add_keys,
+ * fhh_add_keys_bincode or fhh_gen_keys_pair, or after fhh_tree_init (fhh_reset first); those three refuse a
+ * ctx that holds appended keys.
+ * fhh_reserve_clients sizes the device layout for `capacity` clients before the appends. Optional on a
+ * one-GPU ctx: without it the layout starts at the first batch and doubles when full (a copy of the keys
+ * held so far), and a capacity that is not the final count rounded up to 64 costs one compacting copy at
+ * fhh_tree_init; a reservation of the final count costs no copy. FHH_E_ARG if below the current count,
+ * FHH_E_STATE after fhh_tree_init. Required on a multi-device ctx, whose shards' client ranges
+ * (fhh_shard_plan) depend on the total: an append without it returns FHH_E_STATE, one past it FHH_E_ARG,
+ * fhh_tree_init with fewer clients than reserved FHH_E_STATE. fhh_reset drops appended keys and the
+ * reservation. */
+int fhh_reserve_clients(fhh_ctx* ctx, uint64_t capacity);
+int fhh_add_keys_bincode_append(fhh_ctx* ctx, const uint8_t* req, uint64_t len);
+
 /* Leader-side batched `gen_l_inf_ball` keygen on the GPU (ibDCF.rs:84-119,138-188),
  * writing server 0's keys into ctx0 and server 1's into ctx1 (both must be empty and on the
  * same device). Replaces the leader's per-client `add_fuzzy_keys` loop (leader.rs:130-163).
