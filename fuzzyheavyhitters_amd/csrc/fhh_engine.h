@@ -80,6 +80,10 @@ struct PinnedBuf {
         return hipSuccess;
     }
     template <class T> T* as() const { return static_cast<T*>(p); }
+    void swap(PinnedBuf& o) {
+        std::swap(p, o.p);
+        std::swap(bytes, o.bytes);
+    }
 };
 
 struct DimTable {
@@ -187,6 +191,12 @@ struct fhh_ctx {
     }
 };
 
+// the form of ctx's equality tests for caller `who` (gt_plan.h), under its fhh_set_table_row_major switch
+inline GtPlan ctx_gt_plan(const fhh_ctx* ctx, GtCaller who, uint32_t bits, uint32_t kind, uint32_t gc, bool ring_req,
+                          uint64_t nw) {
+    return gt_plan(who, bits, kind, gc, ring_req, ctx->table_row_major != 0, nw);
+}
+
 #define CTX_CHECK(ctx)                                              \
     do {                                                            \
         if (!(ctx)) {                                               \
@@ -265,6 +275,9 @@ void party_destroy(fhh_ctx* ctx);   // fhh_gcot.cpp
 
 // ---- fhh_gcot.cpp (row f1) -------------------------------------------------------------------
 void host_key_schedule(const uint8_t key[16], uint32_t (&rk)[11][4]);
+// [3][128][44] key schedules of 128 base OTs: pairs [128][2][16] -> rows 0 / 1, chosen [128][16] -> row 2
+// (a null source: its rows zero)
+void base_ot_schedules(const uint8_t* pairs, const uint8_t* chosen, uint32_t* rk);
 void words_from_bytes(const uint8_t b[16], uint32_t (&w)[4]);
 uint64_t host_mix64(uint64_t z);
 void gc_level_material(uint64_t prf_seed, uint32_t level, uint8_t key[16], uint8_t delta[16], uint32_t* mask);

@@ -39,6 +39,21 @@ void host_key_schedule(const uint8_t key[16], uint32_t (&rk)[11][4]) {
         for (int c = 0; c < 4; c++) rk[r][c] = w[4 * r + c];
 }
 
+// [3][128][44] key schedules of an OT extension's 128 base OTs: rows 0 / 1 the receiver's, from both seeds
+// of each base OT (pairs [128][2][16]); row 2 the sender's, from its chosen seeds ([128][16]). A null source
+// leaves its rows zero (a party's ctx holds only its own: the other's are never read)
+void base_ot_schedules(const uint8_t* pairs, const uint8_t* chosen, uint32_t* rk) {
+    std::memset(rk, 0, (size_t)3 * 128 * 44 * 4);
+    for (int i = 0; i < 128; i++)
+        for (int b = 0; b < 3; b++) {
+            const uint8_t* key = b < 2 ? pairs : chosen;
+            if (!key) continue;
+            uint32_t w[11][4];
+            host_key_schedule(key + (b < 2 ? (size_t)i * 2 + b : (size_t)i) * 16, w);
+            std::memcpy(rk + ((size_t)b * 128 + i) * 44, w, 44 * 4);
+        }
+}
+
 void words_from_bytes(const uint8_t b[16], uint32_t (&w)[4]) {
     for (int c = 0; c < 4; c++)
         w[c] = (uint32_t)b[4 * c] | ((uint32_t)b[4 * c + 1] << 8) | ((uint32_t)b[4 * c + 2] << 16) |
@@ -133,15 +148,11 @@ hipError_t ot_choices_buffer(fhh_ctx* ctx, uint64_t m, uint32_t** out) {
 // the 3 x 128 base-OT key schedules from host seeds (receiver k_i^0, k_i^1; sender k_i^{s_i}),
 // uploaded and synchronised (the staging vector is reused by the next call)
 int ot_host_keys(fhh_ctx* ctx, const uint8_t seeds[128 * 2 * 16], const uint8_t s[16], const uint32_t** rk_dev) {
-    ctx->ot_rk_host.assign((size_t)3 * 128 * 44, 0);
-    for (int i = 0; i < 128; i++) {
-        const int si = (s[i / 8] >> (i % 8)) & 1;
-        uint32_t rk[11][4];
-        for (int b = 0; b < 3; b++) {
-            host_key_schedule(seeds + (size_t)(i * 2 + (b < 2 ? b : si)) * 16, rk);
-            std::memcpy(ctx->ot_rk_host.data() + ((size_t)b * 128 + i) * 44, rk, 44 * 4);
-        }
-    }
+    uint8_t chosen[128 * 16];
+    for (int i = 0; i < 128; i++)
+        std::memcpy(chosen + 16 * i, seeds + (size_t)(i * 2 + ((s[i / 8] >> (i % 8)) & 1)) * 16, 16);
+    ctx->ot_rk_host.resize((size_t)3 * 128 * 44);
+    base_ot_schedules(seeds, chosen, ctx->ot_rk_host.data());
     HIP_TRY(ctx, ctx->ot_rk.ensure(ctx->ot_rk_host.size() * 4));
     HIP_TRY(ctx, hipMemcpyAsync(ctx->ot_rk.p, ctx->ot_rk_host.data(), ctx->ot_rk_host.size() * 4,
                                 hipMemcpyHostToDevice, ctx->stream));
@@ -570,15 +581,12 @@ static int gt_cot_host(fhh_ctx* ctx, uint64_t n, uint32_t bits, const uint8_t* g
         return ctx->fail(FHH_E_ARG, "gt_cot: NULL argument");
     if (!(base_choice[0] & 1)) return ctx->fail(FHH_E_ARG, "gt_cot: s is the free-XOR Delta: its bit 0 must be 1");
     if (n > 0xFFFFFFFFull) return ctx->fail(FHH_E_ARG, "gt_cot: n must fit 32 bits");
-    // r06: b <= 2 runs the tile-major table kernels on Q / T (the level loop's form), whose OT index wants
-    // plane rows of whole 512-client tiles; b = 3, 4 the row-major labels of k_ot_rows_out (Z_2^32 there:
-    // k_gt_garble_r32 / k_gt_eval_r32, whose node values are u32)
-    // (b = 3, 4 tile-major too, on windows at any nw = ceil(n / 64): the OT index stays; fhh_set_table_row_major
-    // keeps them on the row-major labels)
-    const bool tm = bits <= (uint32_t)kGtTmPadBits || !ctx->table_row_major;
-    const bool val32 = ring32 && !tm;
-    const uint64_t nw = bits <= (uint32_t)kGtTmPadBits ? (n + 511) / 512 * 8 : (n + 63) / 64, npad = 64 * nw,
-                   m = (uint64_t)bits * npad;
+    // the level loop's form of the table (gt_plan.h) at nw = ceil(n / 64); the row-major Z_2^32 kernels'
+    // (k_gt_garble_r32 / k_gt_eval_r32) node values are u32
+    const GtPlan plan = ctx_gt_plan(ctx, GtCaller::kCotHost, bits, 1, 2, ring32, (n + 63) / 64);
+    const bool tm = plan.tile_major;
+    const bool val32 = plan.ring32 && !tm;
+    const uint64_t nw = plan.nw_gc, npad = plan.npad_gc, m = (uint64_t)bits * npad;
     const uint64_t R = 1ull << bits;
     std::vector<uint64_t> planes[2];
     const uint8_t* src[2] = {gb_bits, ev_bits};
@@ -626,7 +634,7 @@ static int gt_cot_host(fhh_ctx* ctx, uint64_t n, uint32_t bits, const uint8_t* g
     g.lab_tm = tm ? 1u : 0u;
     g.ev_ot = 1;
     g.gt_msgs = dm.as<uint64_t>();
-    g.ring32 = ring32 ? 1u : 0u;
+    g.ring32 = plan.ring32 ? 1u : 0u;
     g.sh_gb = dsh.as<uint64_t>();
     HIP_TRY(ctx, launch_gt_garble(g, ctx->stream));
     g.ev_labels = tm ? ctx->ot_buf[0].as<uint4>() : da.as<uint4>();
@@ -654,7 +662,7 @@ static int gt_cot_host(fhh_ctx* ctx, uint64_t n, uint32_t bits, const uint8_t* g
         HIP_TRY(ctx, hipMemcpy(gb_share, dsh.p, n * 8, hipMemcpyDeviceToHost));
         HIP_TRY(ctx, hipMemcpy(ev_share, dsh.as<uint64_t>() + n, n * 8, hipMemcpyDeviceToHost));
     }
-    if (msgs && R > 1 && ring32) {   // SoA [R-1][n] u32 on the device -> [n][R-1] (zero-extended)
+    if (msgs && R > 1 && plan.ring32) {   // SoA [R-1][n] u32 on the device -> [n][R-1] (zero-extended)
         std::vector<uint32_t> h((R - 1) * n);
         HIP_TRY(ctx, hipMemcpy(h.data(), dm.p, h.size() * 4, hipMemcpyDeviceToHost));
         for (uint64_t r = 0; r + 1 < R; r++)
@@ -728,7 +736,7 @@ struct PartyState {
     bool lshare = false;        // r05c (FE levels): the share from the GC output labels, no OT 2
     bool ltable = false;        // r05d (FE levels, bits <= kGtMaxBits): one garbled table per test
     bool lring = false;         // form 2 (ltable): the table's shares, messages and node values in Z_2^32 (u32)
-    bool ltm = false;           // r06 (ltable, bits <= kGtTmPadBits): the table kernels read the labels OT's
+    bool ltm = false;           // r06 (ltable, b <= 2 here: gt_plan.h): the table kernels read the labels OT's
                                 // tile-major Q / T (no row transposes); npad / nw = whole 512-client tiles
     // C = this instance's children: the chunk [c_off, c_off + C) of the level's level_C children
     // (child_begin / child_count); covered = children whose OTs are finished
@@ -816,21 +824,18 @@ int party_begin(fhh_ctx* ctx, int role, uint64_t child_begin, uint64_t child_cou
     P.c_off = b;
     P.C = child_count ? std::min<uint64_t>(child_count, LC - b) : LC;
     P.n = ctx->n;
-    P.npad = ctx->npad;   // (r06 tile-major table: whole 512-client tiles, set below)
-    P.nw = ctx->nw;
     P.bits = 2 * ctx->d;
     P.tests = P.C * P.n;
-    P.per2 = P.last ? 2 : 1;
-    P.lshare = !P.last;
-    P.ltable = P.lshare && P.bits <= (uint32_t)kGtMaxBits && form != 1;   // form 1: the circuit (r05c)
-    P.lring = P.ltable && form == 2;   // form 2: the table over Z_2^32 (the FieldElm level is form 0's)
-    // (bits = 3, 4 stay on the row-major labels here whatever fhh_set_table_row_major says: the tile-major
-    // kernels of that width serve the level loop and fhh_gt_cot*_host only)
-    P.ltm = P.ltable && P.bits <= (uint32_t)kGtTmPadBits;
-    if (P.ltm) {   // plane rows and the OT index over whole 512-client tiles (both parties alike: n is public)
-        P.nw = (ctx->nw + 7) / 8 * 8;
-        P.npad = 64 * P.nw;
-    }
+    // form 1: the circuit (r05c); form 2: the table over Z_2^32 (the FieldElm level is form 0's). The plane
+    // rows and the OT index are both parties' alike: n is public
+    const GtPlan plan = ctx_gt_plan(ctx, GtCaller::kParty, P.bits, last ? 2 : 1, form == 1 ? 3 : 2, form == 2, ctx->nw);
+    P.per2 = plan.per2;
+    P.lshare = plan.lshare;
+    P.ltable = plan.table;
+    P.lring = plan.ring32;
+    P.ltm = plan.tile_major;
+    P.nw = plan.nw_gc;
+    P.npad = plan.npad_gc;
     P.m1 = P.C * P.bits * P.npad;   // OT index (g bits + j) npad + i: the share planes as choice bits
     P.m2 = P.lshare ? 0 : P.tests * P.per2;   // OT 2 (the share OT) at the FieldElm level only
     if (b == 0) P.bytes_sent = 0;   // the level's outgoing bytes, over its chunks
@@ -848,7 +853,7 @@ int party_begin(fhh_ctx* ctx, int role, uint64_t child_begin, uint64_t child_cou
     }
     // the level's node values, one row of n per child (u64 FE, or a BlockPair at the last level); with the
     // fused sums (ltm) only the per-child partials, zeroed at the level's first chunk
-    P.lfused = P.ltm;
+    P.lfused = plan.fused_sums;
     if (b == 0 && P.lfused) {
         HIP_TRY(ctx, P.partials.ensure(std::max<uint64_t>(LC, 1) * 4 * 8));
         HIP_TRY(ctx, hipMemsetAsync(P.partials.p, 0, std::max<uint64_t>(LC, 1) * 4 * 8, ctx->stream));
@@ -883,18 +888,8 @@ void party_session(PartyState& P, int w, const uint8_t* mat, size_t bytes, uint6
 // base OT, sender row 2 from its chosen seeds (the other party's rows stay zero: never read)
 int party_keys(fhh_ctx* ctx, PartyState& P, int w, const uint8_t* pairs /*[128][2][16] or null*/,
                const uint8_t* chosen /*[128][16] or null*/) {
-    P.rk_host.assign((size_t)3 * 128 * 44, 0);
-    for (int i = 0; i < 128; i++) {
-        uint32_t k[11][4];
-        for (int b = 0; b < 2 && pairs; b++) {
-            host_key_schedule(pairs + ((size_t)i * 2 + b) * 16, k);
-            std::memcpy(P.rk_host.data() + ((size_t)b * 128 + i) * 44, k, 44 * 4);
-        }
-        if (chosen) {
-            host_key_schedule(chosen + (size_t)i * 16, k);
-            std::memcpy(P.rk_host.data() + ((size_t)2 * 128 + i) * 44, k, 44 * 4);
-        }
-    }
+    P.rk_host.resize((size_t)3 * 128 * 44);
+    base_ot_schedules(pairs, chosen, P.rk_host.data());
     HIP_TRY(ctx, P.rk[w].ensure(P.rk_host.size() * 4));
     HIP_TRY(ctx, hipMemcpyAsync(P.rk[w].p, P.rk_host.data(), P.rk_host.size() * 4, hipMemcpyHostToDevice, ctx->stream));
     // the staging vector is rewritten by the next call: finish the copy now

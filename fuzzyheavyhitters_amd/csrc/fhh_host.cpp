@@ -8,10 +8,6 @@
 // on the host and never moves state (the reference does O(F) Vec::remove of whole nodes,
 // collect.rs:918-929).
 #include "fhh_engine.h"
-
-#ifndef FHH_GT_FUSED_SUMS
-#define FHH_GT_FUSED_SUMS 1   // r06: the tile-major table kernels add the node values per child themselves
-#endif
 #include "aes_tables.h"
 
 #include <hip/hip_runtime.h>
@@ -25,6 +21,7 @@
 #include <map>
 #include <memory>
 #include <mutex>
+#include <optional>
 #include <thread>
 #include <cstdio>
 #include <cstdlib>
@@ -889,13 +886,7 @@ struct BaseOtProducer {
             std::vector<uint32_t> rk;
             if (!r) {
                 rk.resize((size_t)3 * 128 * 44);
-                for (int i = 0; i < 128; i++) {
-                    uint32_t w[11][4];
-                    for (int b = 0; b < 3; b++) {
-                        host_key_schedule(b < 2 ? &pairs[((size_t)i * 2 + b) * 16] : &chosen[(size_t)i * 16], w);
-                        std::memcpy(&rk[((size_t)b * 128 + i) * 44], w, 44 * 4);
-                    }
-                }
+                base_ot_schedules(pairs.data(), chosen.data(), rk.data());
             }
             const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
             std::lock_guard<std::mutex> lk(mu);
@@ -966,6 +957,49 @@ struct LoopBuffers {
     }
 };
 
+// one device-loop crawl: what its phases (loop_setup .. loop_probe_readback) share
+struct Loop : LoopBuffers {
+    fhh_ctx *c0, *c1, *cs[2];
+    const fhh_sim_config* cfg;
+    uint32_t levels, d;
+    int variant;
+    uint64_t grid_waves;
+    uint64_t thr;
+    uint32_t thr_last;
+    // GC + OT chunk: children per protocol instance, so the level's GC and OT buffers (GtPlan::bytes_per_test
+    // per test) stay within FHH_GC_CHUNK_BYTES (default 64 GiB): one chunk per level at configs[1], ~160
+    // children per chunk at 1M clients
+    uint64_t gc_budget = 64ull << 30;
+    bool record;   // cfg->counts: every level's reduced partials are kept for the host
+    std::optional<PairScope> pair;   // from loop_setup's tree_init on, both servers run on c0's stream
+    Loop(fhh_ctx* a, fhh_ctx* b, const fhh_sim_config* cf, uint32_t lvls, uint64_t t, uint32_t tl)
+        : c0(a), c1(b), cs{a, b}, cfg(cf), levels(lvls), d(a->d), variant(a->variant),
+          grid_waves((uint64_t)a->grid * (expand_threads(a->variant) / 64)), thr(t), thr_last(tl),
+          record(cf->counts != nullptr) {
+        distributed = cf->comm || cf->allreduce;
+        if (const char* e = std::getenv("FHH_GC_CHUNK_BYTES")) gc_budget = std::strtoull(e, nullptr, 10);
+    }
+    // the form of level kind `pmode`'s equality tests (gt_plan.h)
+    GtPlan plan(uint32_t pmode) const {
+        return ctx_gt_plan(c0, GtCaller::kLoop, 2 * d, pmode, cfg->gc, cfg->table_ring32 != 0, c0->nw);
+    }
+};
+
+// one level of the crawl as its phases see it
+struct Level {
+    uint32_t lv;
+    bool last;
+    int par;          // table buffer of the level's parents; the children go to 1 - par
+    uint32_t pmode;   // 0 counts, 1 FE, 2 FieldElm (the last level)
+    uint32_t per;     // partial u64 per child
+    uint64_t C_cap;   // children the buffers hold: grid hint and all-reduce count (the real C is in LoopCtl)
+    bool timed;       // this level's launches are event-timed (fhh_set_timing)
+    Level(const Loop& S, uint32_t l)
+        : lv(l), last(l + 1 == S.levels), par(l & 1), pmode(S.cfg->mode == 0 ? 0 : (last ? 2 : 1)),
+          per(pmode == 0 ? 1 : (pmode == 1 ? 4 : 16)), C_cap((uint64_t)S.F_cap << S.d),
+          timed(S.c0->timing && l % S.c0->timing_every == 0) {}
+};
+
 // wait for the base OTs of OT extension (lv, salt) and copy their key schedules to the next ring
 // slot; returns the slot's device address. The copy is from pageable memory, so it has left the host
 // buffer on return, and the instance is released.
@@ -1000,12 +1034,9 @@ int table_grow(fhh_ctx* ctx, DimTable& T, int buf, size_t cap, size_t keep) {
         HIP_TRY(ctx, hipMemcpyAsync(ny.p, T.y[buf].p, keep * 2 * ctx->nw * 8, hipMemcpyDeviceToDevice, ctx->stream));
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     }
-    std::swap(T.seed[buf].p, ns.p);
-    std::swap(T.seed[buf].bytes, ns.bytes);
-    std::swap(T.t[buf].p, nt.p);
-    std::swap(T.t[buf].bytes, nt.bytes);
-    std::swap(T.y[buf].p, ny.p);
-    std::swap(T.y[buf].bytes, ny.bytes);
+    T.seed[buf].swap(ns);
+    T.t[buf].swap(nt);
+    T.y[buf].swap(ny);
     T.cap[buf] = cap;
     return FHH_OK;
 }
@@ -1032,8 +1063,32 @@ size_t table_entry_bytes(const fhh_ctx* c) { return 2 * c->npad * 16 + 2 * 2 * c
 // that fits on every rank is taken. FHH_TEST_TABLE_BYTES="a0,a1,..." replaces the available bytes of
 // rank r by a_r (the last entry for higher ranks): r = the communicator's rank, or FHH_TEST_RANK on the
 // cfg->allreduce callback path (0 if unset): tests force different free memory per rank with it.
-int loop_entry_cap(fhh_ctx* const (&cs)[2], const fhh_sim_config* cfg, LoopBuffers& B, uint32_t d, uint32_t E_cap,
-                   uint32_t need, uint32_t la, uint32_t& out) {
+// all-reduce `count` u64 from src into dst on the engine stream, over the crawl's transport: the
+// communicator (cfg->comm), or the cfg->allreduce callback on the exchange buffer, which runs on the host:
+// the stream is drained before it
+int loop_allreduce(Loop& S, const uint64_t* src, uint64_t* dst, uint64_t count) {
+    fhh_ctx* c0 = S.c0;
+    const fhh_sim_config* cfg = S.cfg;
+    if (cfg->comm) {
+        std::string err;
+        if (comm_allreduce(cfg->comm, src, dst, count, c0->stream, &err)) return c0->fail(FHH_E_COMM, err);
+        return FHH_OK;
+    }
+    if (!cfg->xchg_dev || cfg->xchg_capacity < count)
+        return c0->fail(FHH_E_ARG, "sim: all-reduce exchange buffer too small");
+    HIP_TRY(c0, hipMemcpyAsync(cfg->xchg_dev, src, count * 8, hipMemcpyDeviceToDevice, c0->stream));
+    const int rc = sync(c0);
+    if (rc) return rc;
+    if (cfg->allreduce(cfg->xchg_dev, count, cfg->allreduce_user) != 0)
+        return c0->fail(FHH_E_CALLBACK, "all-reduce callback failed");
+    HIP_TRY(c0, hipMemcpyAsync(dst, cfg->xchg_dev, count * 8, hipMemcpyDeviceToDevice, c0->stream));
+    return FHH_OK;
+}
+
+int loop_entry_cap(Loop& B, uint32_t need, uint32_t la, uint32_t& out) {
+    fhh_ctx* const(&cs)[2] = B.cs;
+    const fhh_sim_config* cfg = B.cfg;
+    const uint32_t d = B.d, E_cap = B.E_cap;
     size_t free_b = 0, total_b = 0;
     HIP_TRY(cs[0], hipMemGetInfo(&free_b, &total_b));
     size_t held = 0, old_pres = 0, n_tab = 0;   // bytes the tables hold now; largest preserved one
@@ -1074,18 +1129,8 @@ int loop_entry_cap(fhh_ctx* const (&cs)[2], const fhh_sim_config* cfg, LoopBuffe
         HIP_TRY(c0, B.agree.ensure(2 * 3 * 8));
         uint64_t* dv = B.agree.as<uint64_t>();
         HIP_TRY(c0, hipMemcpyAsync(dv, nofit, sizeof nofit, hipMemcpyHostToDevice, c0->stream));
-        if (cfg->comm) {
-            std::string err;
-            if (comm_allreduce(cfg->comm, dv, dv + 3, 3, c0->stream, &err)) return c0->fail(FHH_E_COMM, err);
-        } else {
-            if (!cfg->xchg_dev || cfg->xchg_capacity < 3)
-                return c0->fail(FHH_E_ARG, "sim: all-reduce exchange buffer too small");
-            HIP_TRY(c0, hipMemcpyAsync(cfg->xchg_dev, dv, sizeof nofit, hipMemcpyDeviceToDevice, c0->stream));
-            HIP_TRY(c0, hipStreamSynchronize(c0->stream));
-            if (cfg->allreduce(cfg->xchg_dev, 3, cfg->allreduce_user) != 0)
-                return c0->fail(FHH_E_CALLBACK, "all-reduce callback failed");
-            HIP_TRY(c0, hipMemcpyAsync(dv + 3, cfg->xchg_dev, sizeof nofit, hipMemcpyDeviceToDevice, c0->stream));
-        }
+        const int rc = loop_allreduce(B, dv, dv + 3, 3);
+        if (rc) return rc;
         HIP_TRY(c0, hipMemcpyAsync(nofit, dv + 3, sizeof nofit, hipMemcpyDeviceToHost, c0->stream));
         HIP_TRY(c0, hipStreamSynchronize(c0->stream));
     }
@@ -1105,13 +1150,12 @@ int loop_entry_cap(fhh_ctx* const (&cs)[2], const fhh_sim_config* cfg, LoopBuffe
 int loop_resize(fhh_ctx* c0, LoopBuffers& B, uint32_t E_cap, uint32_t F_cap, uint32_t levels, uint32_t level,
                 bool preserve, uint32_t keep_nodes, uint32_t keep_children, uint32_t per) {
     const uint32_t d = c0->d;
-    const size_t C_old = (size_t)B.F_cap << d, C_new = (size_t)F_cap << d;
+    const size_t C_new = (size_t)F_cap << d;
     HIP_TRY(c0, hipStreamSynchronize(c0->stream));
     for (int b = 0; b < 2; b++) {
         DevBuf nl;
         HIP_TRY(c0, nl.ensure((size_t)d * E_cap * 4));
-        std::swap(B.live[b].p, nl.p);
-        std::swap(B.live[b].bytes, nl.bytes);
+        B.live[b].swap(nl);
         DevBuf np;
         HIP_TRY(c0, np.ensure((size_t)F_cap * d * 4));
         const int keep_par = level & 1;
@@ -1121,8 +1165,7 @@ int loop_resize(fhh_ctx* c0, LoopBuffers& B, uint32_t E_cap, uint32_t F_cap, uin
             HIP_TRY(c0, hipMemcpyAsync(np.p, B.pos[b].p, (size_t)keep_nodes * d * 4, hipMemcpyDeviceToDevice, c0->stream));
             HIP_TRY(c0, hipStreamSynchronize(c0->stream));
         }
-        std::swap(B.pos[b].p, np.p);
-        std::swap(B.pos[b].bytes, np.bytes);
+        B.pos[b].swap(np);
     }
     HIP_TRY(c0, B.mark.ensure((size_t)d * E_cap * 4));
     {
@@ -1140,14 +1183,9 @@ int loop_resize(fhh_ctx* c0, LoopBuffers& B, uint32_t E_cap, uint32_t F_cap, uin
                 HIP_TRY(c0, hipMemcpyAsync(nred.p, B.reduced.p, (size_t)keep_children * per * 8, hipMemcpyDeviceToDevice, c0->stream));
         }
         HIP_TRY(c0, hipStreamSynchronize(c0->stream));
-        std::swap(B.partials.p, npart.p);
-        std::swap(B.partials.bytes, npart.bytes);
-        if (B.distributed) {
-            std::swap(B.reduced.p, nred.p);
-            std::swap(B.reduced.bytes, nred.bytes);
-        }
+        B.partials.swap(npart);
+        if (B.distributed) B.reduced.swap(nred);
     }
-    (void)C_old;
     // hist rows for levels >= level live in a new epoch of stride F_cap
     DevBuf* ep = new DevBuf();
     if (ep->ensure((size_t)(levels - level) * F_cap * 4) != hipSuccess) {
@@ -1162,41 +1200,16 @@ int loop_resize(fhh_ctx* c0, LoopBuffers& B, uint32_t E_cap, uint32_t F_cap, uin
     return FHH_OK;
 }
 
-int sim_crawl_device_loop(fhh_ctx* c0, fhh_ctx* c1, const fhh_sim_config* cfg, uint32_t levels, uint64_t thr,
-                          uint32_t thr_last) {
-    const uint32_t d = c0->d;
-    const int variant = c0->variant;
-    const uint64_t grid_waves = (uint64_t)c0->grid * (expand_threads(variant) / 64);
-    const uint32_t per_level_per = cfg->mode == 0 ? 1 : 4;   // partial u64 per child (non-last)
-    // GC + OT chunk: children per protocol instance, so the level's GC and OT buffers (~400 B per
-    // test at d = 1) stay within FHH_GC_CHUNK_BYTES (default 64 GiB): one chunk per level at
-    // configs[1], ~160 children per chunk at 1M clients
-    uint64_t gc_groups = ~0ull, gc_groups_last = ~0ull;
-    if (cfg->gc) {
-        uint64_t budget = 64ull << 30;
-        if (const char* e = std::getenv("FHH_GC_CHUNK_BYTES")) budget = std::strtoull(e, nullptr, 10);
-        // r06: the d = 1 garbled table on the tile-major labels holds ~140 B per test (T, U, Q 96, rows 24,
-        // node values 16), not the circuit's ~400: larger chunks, one per level at 1M clients
-        // d = 2 on the tile-major labels: T, U, Q 3 x 4 x 16 B and 15 rows of 8 B, ~320 B per test (the row-major
-        // path adds both parties' 4 labels and the node values: the circuit's estimate stays)
-        const bool tm_table = cfg->gc == 2 && 2 * d <= (uint32_t)kGtTmMaxBits &&
-                              (2 * d <= (uint32_t)kGtTmPadBits || !c0->table_row_major);
-        const uint64_t per_test = !tm_table ? 200ull * 2 * d + 2 : 2 * d <= (uint32_t)kGtTmPadBits ? 150ull : 320ull;
-        gc_groups = std::max<uint64_t>(1, budget / (per_test * std::max<uint64_t>(c0->npad, 1)));
-        // the FieldElm level runs the circuit + share C-OT whatever the FE levels run
-        gc_groups_last = std::max<uint64_t>(1, budget / ((200ull * 2 * d + 2) * std::max<uint64_t>(c0->npad, 1)));
-    }
-    // Z_2^32 table shares at the FE levels (2d <= 4): the tile-major table with fused sums, or at d = 2 on the
-    // row-major labels k_gt_garble_r32 / k_gt_eval_r32 with their u32 values summed by k_ring32_child_partials
-    const bool ring32 = cfg->table_ring32 && cfg->gc == 2 && cfg->mode == 1 && 2 * d <= (uint32_t)kGtTmMaxBits &&
-                        FHH_GT_FUSED_SUMS;
-    PhaseClock pc;
-    LoopBuffers B;
-    B.distributed = cfg->comm || cfg->allreduce;
+// ---- the device level loop's phases, in the order sim_crawl_device_loop runs them ----
+
+// table growth, tree_init of both servers, the ctl / sizes / probe buffers, the base-OT producer, k_loop_init
+int loop_setup(Loop& S) {
+    fhh_ctx *c0 = S.c0, *c1 = S.c1;
+    const fhh_sim_config* cfg = S.cfg;
+    const uint32_t d = S.d, levels = S.levels;
     uint32_t cap0 = std::max(cfg->init_capacity ? next_pow2(cfg->init_capacity) : 256u, c0->loop_cap_hint);
     // tables: both buffers of every dim of both servers hold >= E_cap entries
-    fhh_ctx* cs[2] = {c0, c1};
-    for (fhh_ctx* c : cs)
+    for (fhh_ctx* c : S.cs)
         for (uint32_t j = 0; j < d; j++)
             for (int b = 0; b < 2; b++) {
                 int rc = table_grow(c, c->tab[j], b, std::max<size_t>(cap0, c->tab[j].cap[b]), 0);
@@ -1206,12 +1219,12 @@ int sim_crawl_device_loop(fhh_ctx* c0, fhh_ctx* c1, const fhh_sim_config* cfg, u
     if (rc) return rc;
     rc = fhh_tree_init(c1);
     if (rc) return rc;
-    PairScope pair(c0, c1);
-    HIP_TRY(c0, B.ctl.ensure(sizeof(LoopCtl)));
-    HIP_TRY(c0, B.sizes.ensure((size_t)levels * (4 + kMaxDims) * 4));
-    HIP_TRY(c0, hipMemsetAsync(B.sizes.p, 0, (size_t)levels * (4 + kMaxDims) * 4, c0->stream));
-    HIP_TRY(c0, B.ctl_host.ensure(sizeof(LoopCtl)));
-    rc = loop_resize(c0, B, cap0, cap0, levels, 0, false, 0, 0, 1);
+    S.pair.emplace(c0, c1);
+    HIP_TRY(c0, S.ctl.ensure(sizeof(LoopCtl)));
+    HIP_TRY(c0, S.sizes.ensure((size_t)levels * (4 + kMaxDims) * 4));
+    HIP_TRY(c0, hipMemsetAsync(S.sizes.p, 0, (size_t)levels * (4 + kMaxDims) * 4, c0->stream));
+    HIP_TRY(c0, S.ctl_host.ensure(sizeof(LoopCtl)));
+    rc = loop_resize(c0, S, cap0, cap0, levels, 0, false, 0, 0, 1);
     if (rc) return rc;
     if (cfg->gc >= 2 && cfg->base_ot) {
         // the OT extensions of every level and chunk each start with 128 Chou–Orlandi base OTs
@@ -1222,9 +1235,9 @@ int sim_crawl_device_loop(fhh_ctx* c0, fhh_ctx* c1, const fhh_sim_config* cfg, u
             const uint64_t z = host_mix64(cfg->prf_seed ^ (0x626173655f6f74ull + (uint64_t)k));
             std::memcpy(seed + 8 * k, &z, 8);
         }
-        HIP_TRY(c0, B.base_rk.ensure((size_t)LoopBuffers::kBaseRing * 3 * 128 * 44 * 4));
-        B.bot = std::make_unique<BaseOtProducer>(cfg->prf_seed, seed);
-        B.base_ot = true;
+        HIP_TRY(c0, S.base_rk.ensure((size_t)LoopBuffers::kBaseRing * 3 * 128 * 44 * 4));
+        S.bot = std::make_unique<BaseOtProducer>(cfg->prf_seed, seed);
+        S.base_ot = true;
     }
     if (cfg->probe_n_levels) {
         if (cfg->probe_n_levels > LoopBuffers::kMaxProbe || !cfg->probe_levels || !cfg->probe_n_clients ||
@@ -1232,483 +1245,498 @@ int sim_crawl_device_loop(fhh_ctx* c0, fhh_ctx* c1, const fhh_sim_config* cfg, u
             return c0->fail(FHH_E_ARG, "sim_crawl: bad probe arguments");
         for (uint32_t i = 0; i < cfg->probe_n_clients; i++)
             if (cfg->probe_clients[i] >= c0->n) return c0->fail(FHH_E_ARG, "sim_crawl: probe client out of range");
-        HIP_TRY(c0, B.probe_C.ensure((size_t)cfg->probe_n_levels * 4));
-        HIP_TRY(c0, hipMemsetAsync(B.probe_C.p, 0, (size_t)cfg->probe_n_levels * 4, c0->stream));
-        HIP_TRY(c0, B.probe_clients.ensure((size_t)cfg->probe_n_clients * 8));
-        HIP_TRY(c0, hipMemcpyAsync(B.probe_clients.p, cfg->probe_clients, (size_t)cfg->probe_n_clients * 8,
+        HIP_TRY(c0, S.probe_C.ensure((size_t)cfg->probe_n_levels * 4));
+        HIP_TRY(c0, hipMemsetAsync(S.probe_C.p, 0, (size_t)cfg->probe_n_levels * 4, c0->stream));
+        HIP_TRY(c0, S.probe_clients.ensure((size_t)cfg->probe_n_clients * 8));
+        HIP_TRY(c0, hipMemcpyAsync(S.probe_clients.p, cfg->probe_clients, (size_t)cfg->probe_n_clients * 8,
                                    hipMemcpyHostToDevice, c0->stream));
         HIP_TRY(c0, hipStreamSynchronize(c0->stream));
     }
-    {
-        uint32_t* l0[kMaxDims] = {nullptr, nullptr, nullptr, nullptr};
-        for (uint32_t j = 0; j < d; j++) l0[j] = B.live[0].as<uint32_t>() + (size_t)j * B.E_cap;
-        for (uint32_t j = d; j < kMaxDims; j++) l0[j] = l0[0];
-        HIP_TRY(c0, launch_loop_init(B.ctl.as<LoopCtl>(), d, (uint32_t)c0->nw, expand_max_group(variant),
-                                     expand_max_wpi(variant),
-                                     d, 2, grid_waves, B.pos[0].as<uint32_t>(), l0, c0->stream));
-    }
-    pc.mark("setup");
-    const bool record = cfg->counts != nullptr;
-    const uint32_t kBatch = 32;
-    bool prune_only = false;           // resume after growth: prune of this level only
-    for (uint32_t lv = 0; lv < levels;) {
-        const bool last = lv + 1 == levels;
-        const int par = lv & 1;
-        const uint32_t pmode = cfg->mode == 0 ? 0 : (last ? 2 : 1);
-        const uint32_t per = pmode == 0 ? 1 : (pmode == 1 ? 4 : 16);
-        const uint64_t C_cap = (uint64_t)B.F_cap << d;
-        if (!prune_only) {
-            // -- k_expand, both servers, sizes from LoopCtl
-            ExpandLaunch La{};
-            La.njobs = 2 * d;
-            La.jobs_per_ctx = d;
-            La.ctl = B.ctl.as<LoopCtl>();
-            for (int s = 0; s < 2; s++)
-                for (uint32_t j = 0; j < d; j++) {
-                    fhh_ctx* c = cs[s];
-                    DimTable& T = c->tab[j];
-                    ExpandJob& J = La.job[s * d + j];
-                    J.cw_seed = c->cw_seed.as<uint4>();
-                    J.cw_bits = c->cw_bits.as<uint64_t>();
-                    J.src_seed = T.seed[par].as<uint4>();
-                    J.src_t = T.t[par].as<uint64_t>();
-                    J.src_y = T.y[par].as<uint64_t>();
-                    J.dst_seed = T.seed[1 - par].as<uint4>();
-                    J.dst_t = T.t[1 - par].as<uint64_t>();
-                    J.dst_y = T.y[1 - par].as<uint64_t>();
-                    J.live = B.live[par].as<uint32_t>() + (size_t)j * B.E_cap;
-                    J.level = lv;
-                    J.dim = j;
-                    J.K = c->K;
-                    J.npad = (uint32_t)c->npad;
-                    J.nw = (uint32_t)c->nw;
-                }
-            size_t slot = 0;
-            const bool timed = c0->timing && lv % c0->timing_every == 0;
-            if (timed) HIP_TRY(c0, timing_begin(c0, &slot));
-            La.total_items = 1;   // non-zero: the real count comes from LoopCtl
-            HIP_TRY(c0, launch_expand(La, variant, c0->grid, c0->work_counter.as<uint32_t>(), &c0->expand_seq, c0->stream));
-            if (timed) HIP_TRY(c0, timing_end(c0, slot, 0));
-            c0->stats.expand_launches++;
-            for (uint32_t k = 0; k < cfg->probe_n_levels; k++) {
-                if (cfg->probe_levels[k] != lv) continue;
-                const size_t per = (size_t)C_cap * cfg->probe_n_clients * d * 2;
-                HIP_TRY(c0, B.probe_seed[k].ensure(2 * per * 16));
-                HIP_TRY(c0, B.probe_ty[k].ensure(2 * per));
-                B.probe_stride[k] = C_cap;
-                ProbeArgs pr{};
-                for (int s = 0; s < 2; s++)
-                    for (uint32_t j = 0; j < d; j++) {
-                        pr.seed[s][j] = cs[s]->tab[j].seed[1 - par].as<uint4>();
-                        pr.t[s][j] = cs[s]->tab[j].t[1 - par].as<uint64_t>();
-                        pr.y[s][j] = cs[s]->tab[j].y[1 - par].as<uint64_t>();
-                    }
-                pr.parent_pos = B.pos[par].as<uint32_t>();
-                pr.clients = B.probe_clients.as<uint64_t>();
-                pr.ctl = B.ctl.as<LoopCtl>();
-                pr.out_seed = B.probe_seed[k].as<uint4>();
-                pr.out_ty = B.probe_ty[k].as<uint8_t>();
-                pr.out_C = B.probe_C.as<uint32_t>() + k;
-                pr.C_cap = C_cap;
-                pr.npad = c0->npad;
-                pr.nw = c0->nw;
-                pr.n_probe = cfg->probe_n_clients;
-                pr.d = d;
-                HIP_TRY(c0, launch_probe_states(pr, c0->stream));
-            }
-            // -- equality count / simulated OT sums per child
-            ChildArgs a{};
+    uint32_t* l0[kMaxDims] = {nullptr, nullptr, nullptr, nullptr};
+    for (uint32_t j = 0; j < d; j++) l0[j] = S.live[0].as<uint32_t>() + (size_t)j * S.E_cap;
+    for (uint32_t j = d; j < kMaxDims; j++) l0[j] = l0[0];
+    HIP_TRY(c0, launch_loop_init(S.ctl.as<LoopCtl>(), d, (uint32_t)c0->nw, expand_max_group(S.variant),
+                                 expand_max_wpi(S.variant),
+                                 d, 2, S.grid_waves, S.pos[0].as<uint32_t>(), l0, c0->stream));
+    return FHH_OK;
+}
+
+// k_expand, both servers, sizes from LoopCtl; then the parity probe's capture of the level's children
+int level_expand(Loop& S, const Level& L) {
+    fhh_ctx* c0 = S.c0;
+    const fhh_sim_config* cfg = S.cfg;
+    const uint32_t d = S.d;
+    const int par = L.par;
+    ExpandLaunch La{};
+    La.njobs = 2 * d;
+    La.jobs_per_ctx = d;
+    La.ctl = S.ctl.as<LoopCtl>();
+    for (int s = 0; s < 2; s++)
+        for (uint32_t j = 0; j < d; j++) {
+            fhh_ctx* c = S.cs[s];
+            DimTable& T = c->tab[j];
+            ExpandJob& J = La.job[s * d + j];
+            J.cw_seed = c->cw_seed.as<uint4>();
+            J.cw_bits = c->cw_bits.as<uint64_t>();
+            J.src_seed = T.seed[par].as<uint4>();
+            J.src_t = T.t[par].as<uint64_t>();
+            J.src_y = T.y[par].as<uint64_t>();
+            J.dst_seed = T.seed[1 - par].as<uint4>();
+            J.dst_t = T.t[1 - par].as<uint64_t>();
+            J.dst_y = T.y[1 - par].as<uint64_t>();
+            J.live = S.live[par].as<uint32_t>() + (size_t)j * S.E_cap;
+            J.level = L.lv;
+            J.dim = j;
+            J.K = c->K;
+            J.npad = (uint32_t)c->npad;
+            J.nw = (uint32_t)c->nw;
+        }
+    size_t slot = 0;
+    if (L.timed) HIP_TRY(c0, timing_begin(c0, &slot));
+    La.total_items = 1;   // non-zero: the real count comes from LoopCtl
+    HIP_TRY(c0, launch_expand(La, S.variant, c0->grid, c0->work_counter.as<uint32_t>(), &c0->expand_seq, c0->stream));
+    if (L.timed) HIP_TRY(c0, timing_end(c0, slot, 0));
+    c0->stats.expand_launches++;
+    for (uint32_t k = 0; k < cfg->probe_n_levels; k++) {
+        if (cfg->probe_levels[k] != L.lv) continue;
+        const size_t states = (size_t)L.C_cap * cfg->probe_n_clients * d * 2;   // per server
+        HIP_TRY(c0, S.probe_seed[k].ensure(2 * states * 16));
+        HIP_TRY(c0, S.probe_ty[k].ensure(2 * states));
+        S.probe_stride[k] = L.C_cap;
+        ProbeArgs pr{};
+        for (int s = 0; s < 2; s++)
             for (uint32_t j = 0; j < d; j++) {
-                a.s0.t[j] = c0->tab[j].t[1 - par].as<uint64_t>();
-                a.s0.y[j] = c0->tab[j].y[1 - par].as<uint64_t>();
-                a.s1.t[j] = c1->tab[j].t[1 - par].as<uint64_t>();
-                a.s1.y[j] = c1->tab[j].y[1 - par].as<uint64_t>();
+                pr.seed[s][j] = S.cs[s]->tab[j].seed[1 - par].as<uint4>();
+                pr.t[s][j] = S.cs[s]->tab[j].t[1 - par].as<uint64_t>();
+                pr.y[s][j] = S.cs[s]->tab[j].y[1 - par].as<uint64_t>();
             }
-            a.parent_pos = B.pos[par].as<uint32_t>();
-            a.valid = c0->valid.as<uint64_t>();
-            a.C = C_cap;   // grid hint; the real C comes from LoopCtl
-            a.d = d;
-            a.nw = (uint32_t)c0->nw;
-            a.client_base = c0->client_base;
-            a.prf_seed = cfg->prf_seed;
-            a.level = lv;
-            a.n = (uint32_t)c0->n;
-            a.ctl = B.ctl.as<LoopCtl>();
-            uint64_t* part = B.partials.as<uint64_t>();
-            if (cfg->gc && pmode != 0) {
-                // garbled-circuit equality (tree_crawl with gc_sender, collect.rs:419-482): both
-                // servers' share planes, server 0 garbles, server 1 evaluates. The level's tests
-                // run in chunks of gc_groups children (bounded memory at 1M clients; the reference
-                // splits a level's tests over its channels the same way, collect.rs:423-430), each
-                // chunk a fresh protocol instance: its own garbler key / Delta / mask, and its own
-                // row-PRG range of the level's base-OT sessions
-                const uint32_t bits = 2 * d;
-                const bool real_ot = cfg->gc >= 2;
-                // r05c / r05d: at the FE levels the share comes from the circuit's output labels, or (d <= 2,
-                // gc 2) from ONE garbled table per test; r06: for b <= 2 (d = 1) the table kernels read the
-                // labels OT's tile-major Q / T themselves (no k_ot_rows_out), which wants plane rows of
-                // whole 512-client tiles: the planes and the OT index take nw_gc = nw rounded up to 8 words
-                const bool lshare = real_ot && pmode == 1;
-                const bool ltable = lshare && bits <= (uint32_t)kGtMaxBits && cfg->gc == 2;   // gc 3: the circuit
-                // (b = 3, 4: windows at any nw, so nw_gc = nw and the OT indices stay; fhh_set_table_row_major
-                // keeps the row-major labels there)
-                const bool ltm = ltable && bits <= (uint32_t)kGtTmMaxBits &&
-                                 (bits <= (uint32_t)kGtTmPadBits || !c0->table_row_major);
-                const uint64_t nw_gc = ltm && bits <= (uint32_t)kGtTmPadBits ? (c0->nw + 7) / 8 * 8 : c0->nw,
-                               npad_gc = 64 * nw_gc;
-                const size_t plane_bytes = (size_t)C_cap * bits * nw_gc * 8;
-                for (int s = 0; s < 2; s++) HIP_TRY(c0, B.gc_planes[s].ensure(plane_bytes));
-                size_t gc_slot = 0;
-                if (timed) HIP_TRY(c0, timing_begin(c0, &gc_slot));
-                ChildArgs pa = a;
-                pa.plane_nw = (uint32_t)nw_gc;
-                HIP_TRY(c0, launch_share_planes(pa, B.gc_planes[0].as<uint64_t>(), c0->stream));
-                pa.s0 = a.s1;
-                HIP_TRY(c0, launch_share_planes(pa, B.gc_planes[1].as<uint64_t>(), c0->stream));
-                const uint64_t Gc = std::min<uint64_t>(C_cap, pmode == 2 ? gc_groups_last : gc_groups);
-                const uint64_t chunks = (C_cap + Gc - 1) / Gc;
-                const uint64_t tests = Gc * c0->n;
-                const uint32_t per2 = pmode == 1 ? 1 : 2;   // OTs per test of the share conversion
-                const uint64_t m1 = Gc * bits * npad_gc, m2 = tests * per2;
-                // the level's two base-OT sessions (OtSender / OtReceiver::init per level and kind,
-                // collect.rs:454,460): kind 0 the labels OT, kind 1 the share OT; chunk k extends them
-                // from row-PRG block k x (the chunk's blocks), so no two chunks share a pad
-                const uint32_t* rk_ot[2] = {nullptr, nullptr};
-                uint32_t sw_ot[2][4];
-                if (real_ot) {
-                    HIP_TRY(c0, c0->ot_rk.ensure((size_t)2 * 3 * 128 * 44 * 4));
-                    if (B.base_ot) {
-                        // keep the producer well ahead of the enqueueing: the first levels take ~1 ms of
-                        // GPU time against ~9 ms per CO15 instance, so at 4 levels ahead the loop waited
-                        // 0.56-0.59 s per 1M crawl (base_ot_stall_ms); 32 levels = 64 instances, 4.3 MB
-                        // (kind 1, the share OT, runs at the FieldElm level only: the FE levels take their
-                        // share from the circuit's output labels, r05c)
-                        constexpr uint32_t kAhead = 32;
-                        for (uint32_t l = lv; l < std::min(levels, lv + kAhead); l++)
-                            for (uint32_t w = 0; w < (l + 1 == levels ? 2u : 1u); w++) (void)B.bot->request(l, w);
-                    }
-                    for (uint32_t w = 0; w < (pmode == 2 ? 2u : 1u); w++) {
-                        ot_level_choice(cfg->prf_seed, lv, w, sw_ot[w]);
-                        if (B.base_ot) {
-                            rc = upload_base_ot(c0, B, lv, w, &rk_ot[w]);
-                            if (rc) return rc;
-                        } else {
-                            uint32_t* rk = c0->ot_rk.as<uint32_t>() + (size_t)w * 3 * 128 * 44;
-                            HIP_TRY(c0, launch_ot_level_keys(cfg->prf_seed, lv, w, sw_ot[w], rk, c0->stream));
-                            rk_ot[w] = rk;
-                        }
-                    }
-                }
-                // (the garbled table writes no half-gate tables, decoding bits or output bytes)
-                HIP_TRY(c0, B.gc_tables.ensure(ltable ? 16 : (size_t)std::max(bits - 1, 1u) * 2 * tests * 16));
-                // garbler labels: the ideal-OT garbler's only (the r05 garbler folds its string in)
-                HIP_TRY(c0, B.gc_gbl.ensure(real_ot ? 16 : (size_t)(bits + 1) * tests * 16));
-                // ideal OT: the evaluator's active labels [bits][tests]; OT mode: its zero labels (the
-                // labels C-OT's sender messages) at OT index (g bits + j) npad + i (r06 tile-major table: none,
-                // the kernels read Q / T)
-                HIP_TRY(c0, B.gc_evl.ensure(ltm && bits > (uint32_t)kGtTmPadBits
-                                                ? 16
-                                                : std::max<size_t>((size_t)bits * tests, real_ot && !ltm ? m1 : 0) * 16));
-                HIP_TRY(c0, B.gc_decode.ensure(ltable ? 1 : tests));
-                HIP_TRY(c0, B.gc_out.ensure(ltable ? 1 : tests));
-                for (uint64_t k = 0; k < chunks; k++) {
-                    const uint64_t g_off = k * Gc;
-                    fhh_gc_batch gb{};
-                    gb.groups = Gc;
-                    gb.clients = (uint32_t)c0->n;
-                    gb.words = (uint32_t)nw_gc;
-                    gb.bits = bits;
-                    gc_chunk_material(cfg->prf_seed, lv, k, gb.label_key, gb.delta, &gb.mask);
-                    gb.gate_base = (uint64_t)lv << 40;   // the level in the gate tweaks (party_gate_base)
-                    gb.gb_planes_dev = B.gc_planes[0].as<uint64_t>();
-                    gb.ev_planes_dev = B.gc_planes[1].as<uint64_t>();
-                    gb.tables_dev = B.gc_tables.as<uint8_t>();
-                    gb.gb_labels_dev = B.gc_gbl.as<uint8_t>();
-                    gb.ev_labels_dev = B.gc_evl.as<uint8_t>();
-                    gb.decode_dev = B.gc_decode.as<uint8_t>();
-                    gb.out_dev = B.gc_out.as<uint8_t>();
-                    GcArgs g{};
-                    rc = gc_args(c0, &gb, g);
-                    if (rc) return rc;
-                    g.ctl = B.ctl.as<LoopCtl>();
-                    g.g_off = g_off;
-                    if (real_ot) {
-                        // 1. the evaluator's input labels by correlated OT (gb_set_fancy_inputs /
-                        // ev_set_fancy_inputs, equalitytest.rs:67-82,108-119): server 1's choice bits are
-                        // its share planes [C][bits][nw] from the chunk's first group on, as they stand
-                        // (m1 a multiple of 128: npad of 64, bits even). The IKNP correlation is the label
-                        // pair (r05b, OtArgs mode 4): server 0's q_j is the zero label, server 1's t_j =
-                        // q_j ^ r_j s the active one, with the labels session's s (colour bit set) as the
-                        // circuit's Delta; server 0's string and mask fold into the circuit
-                        // (k_gc_garble_cot: no label is drawn, no reply is sent)
-                        if (!ltm) HIP_TRY(c0, B.gc_evact.ensure(m1 * 16));
-                        for (int c = 0; c < 4; c++) g.delta[c] = sw_ot[0][c];
-                        OtArgs a1{};
-                        a1.mode = ltm ? 5 : 4;
-                        a1.rk = rk_ot[0];
-                        for (int c = 0; c < 4; c++) a1.s[c] = sw_ot[0][c];
-                        a1.choices = B.gc_planes[1].as<uint32_t>() + g_off * bits * nw_gc * 2;
-                        a1.ctr_off = k * ot_session_blocks(m1);
-                        a1.sx = ltm ? nullptr : B.gc_evl.p;
-                        a1.out = ltm ? nullptr : B.gc_evact.as<uint4>();
-                        a1.ctl = B.ctl.as<LoopCtl>();
-                        a1.per_group = npad_gc * bits;
-                        a1.g_off = g_off;
-                        a1.ss_k = cfg->ot_ss_k;
-                        rc = ot_run(c0, a1, m1, nullptr);
-                        if (rc) return rc;
-                        g.ev_ot = 1;
-                        if (ltm) {   // the table kernels on the tile-major Q (garbler) / T (evaluator)
-                            g.lab_tm = 1;
-                            g.ev_labels = c0->ot_buf[2].as<uint4>();
-                        }
-                    }
-                    // r05c: at the FE levels the share comes from the circuit's output labels (W_0 and
-                    // W_0 ^ Delta of o = eq ^ mask in the share C-OT's roles): server 0's node value r1 and
-                    // the 8-B y from k_gc_garble_cot, server 1's value from k_gc_eval — no second OT.
-                    // r05d: tests of <= kGtMaxBits bits (d <= 2) take the share from ONE garbled table per
-                    // test (k_gt_garble / k_gt_eval: 2^bits + 1 AES instead of the half-gates chain's)
-                    if (ltable) {
-                        // r06 (tile-major table): the kernels add the node values per child into the level's
-                        // partials themselves (no stored values, no k_child_sums_fe pass)
-                        const bool fused = ltm && FHH_GT_FUSED_SUMS;
-                        if (!fused) for (int sv = 0; sv < 2; sv++) HIP_TRY(c0, B.gc_val[sv].ensure(tests * 8));
-                        HIP_TRY(c0, B.gc_msgs.ensure(tests * (((size_t)1 << bits) - 1) * 8));
-                        g.gt_msgs = B.gc_msgs.as<uint64_t>();
-                        g.node_partials = ltm && FHH_GT_FUSED_SUMS ? part : nullptr;
-                        g.node_off = 0;
-                        g.ring32 = ring32 ? 1u : 0u;   // (row-major: u32 values [tests] in gc_val, u32 messages)
-                        g.sh_gb = fused ? nullptr : B.gc_val[0].as<uint64_t>();
-                        HIP_TRY(c0, launch_gt_garble(g, c0->stream));
-                        g.ev_labels = ltm ? c0->ot_buf[0].as<uint4>() : B.gc_evact.as<uint4>();
-                        g.sh_gb = nullptr;
-                        g.sh_ev = fused ? nullptr : B.gc_val[1].as<uint64_t>();
-                        HIP_TRY(c0, launch_gt_eval(g, c0->stream));
-                        if (ring32 && !fused)   // the row-major Z_2^32 values into the partials' low sums
-                            for (uint32_t sv = 0; sv < 2; sv++)
-                                HIP_TRY(c0, launch_ring32_child_partials(B.gc_val[sv].as<uint32_t>(), c0->n, Gc,
-                                                                         B.ctl.as<LoopCtl>(), g_off, part, 2 * sv,
-                                                                         c0->stream));
-                    } else if (lshare) {
-                        for (int sv = 0; sv < 2; sv++) HIP_TRY(c0, B.gc_val[sv].ensure(tests * 8));
-                        HIP_TRY(c0, B.gc_y.ensure(tests * 8));
-                        g.sh_gb = B.gc_val[0].as<uint64_t>();
-                        g.sh_y = B.gc_y.as<uint64_t>();
-                    }
-                    if (!ltable) {
-                        HIP_TRY(c0, launch_gc_garble(g, c0->stream));
-                        if (real_ot) {
-                            g.ev_labels = B.gc_evact.as<uint4>();
-                            g.sh_gb = nullptr;
-                            if (lshare) {
-                                g.sh_ev = B.gc_val[1].as<uint64_t>();
-                            } else {
-                                // k_gc_eval ballot-packs its outputs as the share-conversion OT's choice words
-                                uint32_t* och = nullptr;
-                                HIP_TRY(c0, ot_choices_buffer(c0, m2, &och));
-                                g.out_packed = och;
-                                g.out_dup = per2;
-                            }
-                        }
-                        HIP_TRY(c0, launch_gc_eval(g, c0->stream));
-                    }
-                    ChildArgs ca = a;   // this chunk's children
-                    ca.c_off = g_off;
-                    ca.c_cnt = Gc;
-                    ca.gc_out = g.out;
-                    ca.gc_N = g.N;
-                    ca.gc_mask = g.mask;
-                    if (lshare) {
-                        ca.ot_val[0] = B.gc_val[0].p;
-                        ca.ot_val[1] = B.gc_val[1].p;
-                    } else if (real_ot) {
-                        // 2. the share conversion by correlated OT (collect.rs:846-876 at the last level,
-                        // where a FieldElm travels as a BlockPair = 2 OTs): server 0's pair is
-                        // (H(q_j), H(q_j) +- 1) ordered by its mask, its node value r1 = H(q_j) + mask;
-                        // server 1 chooses with its GC output bit
-                        const size_t vb = pmode == 1 ? 8 : 16;
-                        for (int sv = 0; sv < 2; sv++) HIP_TRY(c0, B.gc_val[sv].ensure(m2 * vb));
-                        OtArgs a2{};
-                        a2.mode = pmode == 1 ? 2 : 3;
-                        a2.mask = g.mask;
-                        a2.rk = rk_ot[1];
-                        for (int c = 0; c < 4; c++) a2.s[c] = sw_ot[1][c];
-                        a2.choices = g.out_packed;
-                        a2.ctr_off = k * ot_session_blocks(m2);
-                        a2.sx = B.gc_val[0].p;
-                        a2.out = B.gc_val[1].as<uint4>();
-                        a2.ctl = B.ctl.as<LoopCtl>();
-                        a2.per_group = (uint64_t)c0->n * per2;
-                        a2.g_off = g_off;
-                        a2.ss_k = cfg->ot_ss_k;
-                        rc = ot_run(c0, a2, m2, nullptr);
-                        if (rc) return rc;
-                        ca.ot_val[0] = B.gc_val[0].p;
-                        ca.ot_val[1] = B.gc_val[1].p;
-                    }
-                    // the chunk's children's sums (FE: atomics into the partials k_prune zeroed;
-                    // FE255: one store per child)
-                    if (pmode == 1) {
-                        if (!(ltm && FHH_GT_FUSED_SUMS) && !(ltable && ring32))
-                            HIP_TRY(c0, launch_child_sums_fe(ca, part, c0->stream, false));
-                    } else {
-                        HIP_TRY(c0, launch_child_sums_fe255(ca, part, c0->stream));
-                    }
-                }
-                if (timed) HIP_TRY(c0, timing_end(c0, gc_slot, kGcotTag));
-            } else if (pmode == 0) {
-                HIP_TRY(c0, launch_eq_count(a, part, c0->stream));
-            } else if (pmode == 1) {
-                HIP_TRY(c0, launch_child_sums_fe(a, part, c0->stream, false));
+        pr.parent_pos = S.pos[par].as<uint32_t>();
+        pr.clients = S.probe_clients.as<uint64_t>();
+        pr.ctl = S.ctl.as<LoopCtl>();
+        pr.out_seed = S.probe_seed[k].as<uint4>();
+        pr.out_ty = S.probe_ty[k].as<uint8_t>();
+        pr.out_C = S.probe_C.as<uint32_t>() + k;
+        pr.C_cap = L.C_cap;
+        pr.npad = c0->npad;
+        pr.nw = c0->nw;
+        pr.n_probe = cfg->probe_n_clients;
+        pr.d = d;
+        HIP_TRY(c0, launch_probe_states(pr, c0->stream));
+    }
+    return FHH_OK;
+}
+
+// what a level's GC + OT chunks share: set once per level by level_gc_tests
+struct GcLevel {
+    GtPlan p;
+    uint32_t bits;
+    uint64_t Gc, tests;     // children per chunk, and their tests
+    uint64_t m1, m2;        // OTs per chunk: the labels OT, the share OT
+    // the level's two base-OT sessions (OtSender / OtReceiver::init per level and kind,
+    // collect.rs:454,460): kind 0 the labels OT, kind 1 the share OT; chunk k extends them
+    // from row-PRG block k x (the chunk's blocks), so no two chunks share a pad
+    const uint32_t* rk_ot[2];
+    uint32_t sw_ot[2][4];
+    ChildArgs a;            // the level's children (level_tests)
+};
+
+// chunk k's labels OT: the evaluator's labels into gc_evact (row-major), or left in the OT's tile-major Q / T
+int chunk_labels_ot(Loop& S, const GcLevel& G, uint64_t k, GcArgs& g) {
+    fhh_ctx* c0 = S.c0;
+    const GtPlan& p = G.p;
+    // 1. the evaluator's input labels by correlated OT (gb_set_fancy_inputs /
+    // ev_set_fancy_inputs, equalitytest.rs:67-82,108-119): server 1's choice bits are
+    // its share planes [C][bits][nw] from the chunk's first group on, as they stand
+    // (m1 a multiple of 128: npad of 64, bits even). The IKNP correlation is the label
+    // pair (r05b, OtArgs mode 4): server 0's q_j is the zero label, server 1's t_j =
+    // q_j ^ r_j s the active one, with the labels session's s (colour bit set) as the
+    // circuit's Delta; server 0's string and mask fold into the circuit
+    // (k_gc_garble_cot: no label is drawn, no reply is sent)
+    if (!p.tile_major) HIP_TRY(c0, S.gc_evact.ensure(G.m1 * 16));
+    for (int c = 0; c < 4; c++) g.delta[c] = G.sw_ot[0][c];
+    OtArgs a1{};
+    a1.mode = p.tile_major ? 5 : 4;
+    a1.rk = G.rk_ot[0];
+    for (int c = 0; c < 4; c++) a1.s[c] = G.sw_ot[0][c];
+    a1.choices = S.gc_planes[1].as<uint32_t>() + g.g_off * G.bits * p.nw_gc * 2;
+    a1.ctr_off = k * ot_session_blocks(G.m1);
+    a1.sx = p.tile_major ? nullptr : S.gc_evl.p;
+    a1.out = p.tile_major ? nullptr : S.gc_evact.as<uint4>();
+    a1.ctl = S.ctl.as<LoopCtl>();
+    a1.per_group = p.npad_gc * G.bits;
+    a1.g_off = g.g_off;
+    a1.ss_k = S.cfg->ot_ss_k;
+    int rc = ot_run(c0, a1, G.m1, nullptr);
+    if (rc) return rc;
+    g.ev_ot = 1;
+    if (p.tile_major) {   // the table kernels on the tile-major Q (garbler) / T (evaluator)
+        g.lab_tm = 1;
+        g.ev_labels = c0->ot_buf[2].as<uint4>();
+    }
+    return FHH_OK;
+}
+
+// one chunk (children [k Gc, (k + 1) Gc)) of a level's tests, a fresh protocol instance: labels OT ->
+// garble / evaluate (table or circuit) -> share OT -> the children's sums
+int gc_chunk(Loop& S, const Level& L, const GcLevel& G, uint64_t k) {
+    fhh_ctx* c0 = S.c0;
+    const fhh_sim_config* cfg = S.cfg;
+    const GtPlan& p = G.p;
+    const uint32_t bits = G.bits, pmode = L.pmode;
+    const uint64_t Gc = G.Gc, tests = G.tests, m2 = G.m2;
+    uint64_t* part = S.partials.as<uint64_t>();
+    const uint64_t g_off = k * Gc;
+    fhh_gc_batch gb{};
+    gb.groups = Gc;
+    gb.clients = (uint32_t)c0->n;
+    gb.words = (uint32_t)p.nw_gc;
+    gb.bits = bits;
+    gc_chunk_material(cfg->prf_seed, L.lv, k, gb.label_key, gb.delta, &gb.mask);
+    gb.gate_base = (uint64_t)L.lv << 40;   // the level in the gate tweaks (party_gate_base)
+    gb.gb_planes_dev = S.gc_planes[0].as<uint64_t>();
+    gb.ev_planes_dev = S.gc_planes[1].as<uint64_t>();
+    gb.tables_dev = S.gc_tables.as<uint8_t>();
+    gb.gb_labels_dev = S.gc_gbl.as<uint8_t>();
+    gb.ev_labels_dev = S.gc_evl.as<uint8_t>();
+    gb.decode_dev = S.gc_decode.as<uint8_t>();
+    gb.out_dev = S.gc_out.as<uint8_t>();
+    GcArgs g{};
+    int rc = gc_args(c0, &gb, g);
+    if (rc) return rc;
+    g.ctl = S.ctl.as<LoopCtl>();
+    g.g_off = g_off;
+    if (p.real_ot && (rc = chunk_labels_ot(S, G, k, g))) return rc;
+    // r05c: at the FE levels the share comes from the circuit's output labels (W_0 and
+    // W_0 ^ Delta of o = eq ^ mask in the share C-OT's roles): server 0's node value r1 and
+    // the 8-B y from k_gc_garble_cot, server 1's value from k_gc_eval — no second OT.
+    // r05d: the table's tests (GtPlan::table) take the share from ONE garbled table per test
+    if (p.table) {
+        // r06 (tile-major table): the kernels add the node values per child into the level's
+        // partials themselves (no stored values, no k_child_sums_fe pass)
+        const bool fused = p.fused_sums;
+        if (!fused) for (int sv = 0; sv < 2; sv++) HIP_TRY(c0, S.gc_val[sv].ensure(tests * 8));
+        HIP_TRY(c0, S.gc_msgs.ensure(tests * (((size_t)1 << bits) - 1) * 8));
+        g.gt_msgs = S.gc_msgs.as<uint64_t>();
+        g.node_partials = fused ? part : nullptr;
+        g.node_off = 0;
+        g.ring32 = p.ring32 ? 1u : 0u;   // (row-major: u32 values [tests] in gc_val, u32 messages)
+        g.sh_gb = fused ? nullptr : S.gc_val[0].as<uint64_t>();
+        HIP_TRY(c0, launch_gt_garble(g, c0->stream));
+        g.ev_labels = p.tile_major ? c0->ot_buf[0].as<uint4>() : S.gc_evact.as<uint4>();
+        g.sh_gb = nullptr;
+        g.sh_ev = fused ? nullptr : S.gc_val[1].as<uint64_t>();
+        HIP_TRY(c0, launch_gt_eval(g, c0->stream));
+        if (p.ring32 && !fused)   // the row-major Z_2^32 values into the partials' low sums
+            for (uint32_t sv = 0; sv < 2; sv++)
+                HIP_TRY(c0, launch_ring32_child_partials(S.gc_val[sv].as<uint32_t>(), c0->n, Gc,
+                                                         S.ctl.as<LoopCtl>(), g_off, part, 2 * sv,
+                                                         c0->stream));
+    } else if (p.lshare) {
+        for (int sv = 0; sv < 2; sv++) HIP_TRY(c0, S.gc_val[sv].ensure(tests * 8));
+        HIP_TRY(c0, S.gc_y.ensure(tests * 8));
+        g.sh_gb = S.gc_val[0].as<uint64_t>();
+        g.sh_y = S.gc_y.as<uint64_t>();
+    }
+    if (!p.table) {
+        HIP_TRY(c0, launch_gc_garble(g, c0->stream));
+        if (p.real_ot) {
+            g.ev_labels = S.gc_evact.as<uint4>();
+            g.sh_gb = nullptr;
+            if (p.lshare) {
+                g.sh_ev = S.gc_val[1].as<uint64_t>();
             } else {
-                HIP_TRY(c0, launch_child_sums_fe255(a, part, c0->stream));
-            }
-            // -- cross-rank sum (client-sharded multi-GPU)
-            // (the count is the capacity bound: entries past C are never read)
-            if (cfg->comm) {
-                std::string err;
-                size_t ar_slot = 0;
-                if (timed) HIP_TRY(c0, timing_begin(c0, &ar_slot));
-                if (comm_allreduce(cfg->comm, part, B.red(), C_cap * per, c0->stream, &err))
-                    return c0->fail(FHH_E_COMM, err);
-                if (timed) HIP_TRY(c0, timing_end(c0, ar_slot, kAllreduceTag));
-            } else if (cfg->allreduce) {
-                const uint64_t count = C_cap * per;
-                if (!cfg->xchg_dev || cfg->xchg_capacity < count)
-                    return c0->fail(FHH_E_ARG, "sim: all-reduce exchange buffer too small");
-                HIP_TRY(c0, hipMemcpyAsync(cfg->xchg_dev, part, count * 8, hipMemcpyDeviceToDevice, c0->stream));
-                rc = sync(c0);
-                if (rc) return rc;
-                if (cfg->allreduce(cfg->xchg_dev, count, cfg->allreduce_user) != 0)
-                    return c0->fail(FHH_E_CALLBACK, "all-reduce callback failed");
-                HIP_TRY(c0, hipMemcpyAsync(B.red(), cfg->xchg_dev, count * 8, hipMemcpyDeviceToDevice, c0->stream));
-            }
-            if (record) {
-                const size_t off = B.rec_off.empty() ? 0 : B.rec_off.back() + (size_t)B.rec_stride.back();
-                const size_t need = (off + C_cap * per) * 8;
-                if (B.rec.bytes < need) {
-                    PinnedBuf nb;
-                    HIP_TRY(c0, hipStreamSynchronize(c0->stream));
-                    HIP_TRY(c0, nb.ensure(std::max(need * 2, (size_t)1 << 20)));
-                    if (B.rec.p) std::memcpy(nb.p, B.rec.p, B.rec.bytes);
-                    std::swap(B.rec.p, nb.p);
-                    std::swap(B.rec.bytes, nb.bytes);
-                }
-                B.rec_off.resize(lv + 1);
-                B.rec_stride.resize(lv + 1);
-                B.rec_off[lv] = off;
-                B.rec_stride[lv] = (uint32_t)(C_cap * per);   // u64 words recorded for this level
-                // mode 0: counts; FE: the 4 limbs; FE255: the 16 limbs (v0 - v1 derived at the end)
-                const size_t cpy = (size_t)C_cap * per * 8;
-                HIP_TRY(c0, hipMemcpyAsync(B.rec.as<uint64_t>() + off, B.red(), cpy, hipMemcpyDeviceToHost, c0->stream));
+                // k_gc_eval ballot-packs its outputs as the share-conversion OT's choice words
+                uint32_t* och = nullptr;
+                HIP_TRY(c0, ot_choices_buffer(c0, m2, &och));
+                g.out_packed = och;
+                g.out_dup = p.per2;
             }
         }
-        prune_only = false;
-        // -- leader keep decision + prune (or final list at the last level)
-        if (last) HIP_TRY(c0, B.final_vals.ensure((size_t)B.F_cap * 20 * 4));
-        PruneArgs pa{};
-        pa.ctl = B.ctl.as<LoopCtl>();
-        pa.partials = B.red();
-        pa.mode = pmode;
-        pa.d = d;
-        pa.thr = thr;
-        pa.thr_last = thr_last;
-        pa.last = last ? 1 : 0;
-        pa.pos_in = B.pos[par].as<uint32_t>();
-        pa.pos_out = B.pos[1 - par].as<uint32_t>();
-        for (uint32_t j = 0; j < kMaxDims; j++)
-            pa.live_out[j] = B.live[1 - par].as<uint32_t>() + (size_t)std::min(j, d - 1) * B.E_cap;
-        pa.mark = B.mark.as<uint32_t>();
-        pa.hist_out = B.hist_ptr[lv];
-        pa.sizes_out = B.sizes.as<uint32_t>() + (size_t)lv * (4 + kMaxDims);
-        pa.final_vals = last ? B.final_vals.as<uint32_t>() : nullptr;
-        pa.E_cap = B.E_cap;
-        pa.F_cap = B.F_cap;
-        pa.level = lv;
-        pa.nw = (uint32_t)c0->nw;
-        pa.njobs_per_ctx = d;
-        pa.nctx = 2;
-        pa.grid_waves = grid_waves;
-        pa.unit = (uint32_t)c0->nw;
-        pa.max_group = expand_max_group(variant);
-        pa.max_wpi = expand_max_wpi(variant);
-        pa.zero_partials = (cfg->mode != 0 && !last) ? B.partials.as<uint64_t>() : nullptr;
-        pa.ring32 = ring32 && !last ? 1u : 0u;
-        pa.zero_count = (uint64_t)C_cap * 4;
-        HIP_TRY(c0, launch_prune(pa, c0->stream));
-        lv++;
-        if (lv % kBatch == 0 || lv == levels) {
-            HIP_TRY(c0, hipMemcpyAsync(B.ctl_host.p, B.ctl.p, sizeof(LoopCtl), hipMemcpyDeviceToHost, c0->stream));
-            rc = sync(c0);
+        HIP_TRY(c0, launch_gc_eval(g, c0->stream));
+    }
+    ChildArgs ca = G.a;   // this chunk's children
+    ca.c_off = g_off;
+    ca.c_cnt = Gc;
+    ca.gc_out = g.out;
+    ca.gc_N = g.N;
+    ca.gc_mask = g.mask;
+    if (p.real_ot && !p.lshare) {
+        // 2. the share conversion by correlated OT (collect.rs:846-876 at the last level,
+        // where a FieldElm travels as a BlockPair = 2 OTs): server 0's pair is
+        // (H(q_j), H(q_j) +- 1) ordered by its mask, its node value r1 = H(q_j) + mask;
+        // server 1 chooses with its GC output bit
+        const size_t vb = pmode == 1 ? 8 : 16;
+        for (int sv = 0; sv < 2; sv++) HIP_TRY(c0, S.gc_val[sv].ensure(m2 * vb));
+        OtArgs a2{};
+        a2.mode = pmode == 1 ? 2 : 3;
+        a2.mask = g.mask;
+        a2.rk = G.rk_ot[1];
+        for (int c = 0; c < 4; c++) a2.s[c] = G.sw_ot[1][c];
+        a2.choices = g.out_packed;
+        a2.ctr_off = k * ot_session_blocks(m2);
+        a2.sx = S.gc_val[0].p;
+        a2.out = S.gc_val[1].as<uint4>();
+        a2.ctl = S.ctl.as<LoopCtl>();
+        a2.per_group = (uint64_t)c0->n * p.per2;
+        a2.g_off = g_off;
+        a2.ss_k = cfg->ot_ss_k;
+        rc = ot_run(c0, a2, m2, nullptr);
+        if (rc) return rc;
+    }
+    if (p.real_ot) {   // both servers' node values: the label shares' or the share OT's
+        ca.ot_val[0] = S.gc_val[0].p;
+        ca.ot_val[1] = S.gc_val[1].p;
+    }
+    // the chunk's children's sums (FE: atomics into the partials k_prune zeroed;
+    // FE255: one store per child)
+    if (pmode == 1) {
+        if (!p.fused_sums && !p.ring32) HIP_TRY(c0, launch_child_sums_fe(ca, part, c0->stream, false));
+    } else {
+        HIP_TRY(c0, launch_child_sums_fe255(ca, part, c0->stream));
+    }
+    return FHH_OK;
+}
+
+// garbled-circuit equality (tree_crawl with gc_sender, collect.rs:419-482): both
+// servers' share planes, server 0 garbles, server 1 evaluates. The level's tests
+// run in chunks of Gc children (bounded memory at 1M clients; the reference
+// splits a level's tests over its channels the same way, collect.rs:423-430), each
+// chunk a fresh protocol instance: its own garbler key / Delta / mask, and its own
+// row-PRG range of the level's base-OT sessions. What does not depend on the chunk is done here:
+// the planes, the base-OT requests and uploads, the buffers
+int level_gc_tests(Loop& S, const Level& L, const ChildArgs& a) {
+    fhh_ctx* c0 = S.c0;
+    const fhh_sim_config* cfg = S.cfg;
+    GcLevel G{};
+    G.p = S.plan(L.pmode);
+    G.a = a;
+    const GtPlan& p = G.p;
+    const uint32_t bits = G.bits = 2 * S.d;
+    const size_t plane_bytes = (size_t)L.C_cap * bits * p.nw_gc * 8;
+    for (int s = 0; s < 2; s++) HIP_TRY(c0, S.gc_planes[s].ensure(plane_bytes));
+    size_t gc_slot = 0;
+    if (L.timed) HIP_TRY(c0, timing_begin(c0, &gc_slot));
+    ChildArgs pa = a;
+    pa.plane_nw = (uint32_t)p.nw_gc;
+    HIP_TRY(c0, launch_share_planes(pa, S.gc_planes[0].as<uint64_t>(), c0->stream));
+    pa.s0 = a.s1;
+    HIP_TRY(c0, launch_share_planes(pa, S.gc_planes[1].as<uint64_t>(), c0->stream));
+    const uint64_t Gc = G.Gc = std::min<uint64_t>(
+        L.C_cap, std::max<uint64_t>(1, S.gc_budget / (p.bytes_per_test * std::max<uint64_t>(c0->npad, 1))));
+    const uint64_t chunks = (L.C_cap + Gc - 1) / Gc;
+    const uint64_t tests = G.tests = Gc * c0->n;
+    const uint64_t m1 = G.m1 = Gc * bits * p.npad_gc;
+    G.m2 = tests * p.per2;
+    if (p.real_ot) {
+        HIP_TRY(c0, c0->ot_rk.ensure((size_t)2 * 3 * 128 * 44 * 4));
+        if (S.base_ot) {
+            // keep the producer well ahead of the enqueueing: the first levels take ~1 ms of
+            // GPU time against ~9 ms per CO15 instance, so at 4 levels ahead the loop waited
+            // 0.56-0.59 s per 1M crawl (base_ot_stall_ms); 32 levels = 64 instances, 4.3 MB
+            // (kind 1, the share OT, runs at the FieldElm level only: the FE levels take their
+            // share from the circuit's output labels, r05c)
+            constexpr uint32_t kAhead = 32;
+            for (uint32_t l = L.lv; l < std::min(S.levels, L.lv + kAhead); l++)
+                for (uint32_t w = 0; w < (l + 1 == S.levels ? 2u : 1u); w++) (void)S.bot->request(l, w);
+        }
+        for (uint32_t w = 0; w < (L.pmode == 2 ? 2u : 1u); w++) {
+            ot_level_choice(cfg->prf_seed, L.lv, w, G.sw_ot[w]);
+            if (S.base_ot) {
+                int rc = upload_base_ot(c0, S, L.lv, w, &G.rk_ot[w]);
+                if (rc) return rc;
+            } else {
+                uint32_t* rk = c0->ot_rk.as<uint32_t>() + (size_t)w * 3 * 128 * 44;
+                HIP_TRY(c0, launch_ot_level_keys(cfg->prf_seed, L.lv, w, G.sw_ot[w], rk, c0->stream));
+                G.rk_ot[w] = rk;
+            }
+        }
+    }
+    // (the garbled table writes no half-gate tables, decoding bits or output bytes)
+    HIP_TRY(c0, S.gc_tables.ensure(p.table ? 16 : (size_t)std::max(bits - 1, 1u) * 2 * tests * 16));
+    // garbler labels: the ideal-OT garbler's only (the r05 garbler folds its string in)
+    HIP_TRY(c0, S.gc_gbl.ensure(p.real_ot ? 16 : (size_t)(bits + 1) * tests * 16));
+    // ideal OT: the evaluator's active labels [bits][tests]; OT mode: its zero labels (the
+    // labels C-OT's sender messages) at OT index (g bits + j) npad + i (r06 tile-major table: none,
+    // the kernels read Q / T)
+    HIP_TRY(c0, S.gc_evl.ensure(p.windows ? 16
+                                          : std::max<size_t>((size_t)bits * tests, p.real_ot && !p.tile_major ? m1 : 0) * 16));
+    HIP_TRY(c0, S.gc_decode.ensure(p.table ? 1 : tests));
+    HIP_TRY(c0, S.gc_out.ensure(p.table ? 1 : tests));
+    for (uint64_t k = 0; k < chunks; k++) {
+        int rc = gc_chunk(S, L, G, k);
+        if (rc) return rc;
+    }
+    if (L.timed) HIP_TRY(c0, timing_end(c0, gc_slot, kGcotTag));
+    return FHH_OK;
+}
+
+// equality count / simulated OT sums per child, or the GC + OT protocol (cfg->gc)
+int level_tests(Loop& S, const Level& L) {
+    fhh_ctx *c0 = S.c0, *c1 = S.c1;
+    const int par = L.par;
+    ChildArgs a{};
+    for (uint32_t j = 0; j < S.d; j++) {
+        a.s0.t[j] = c0->tab[j].t[1 - par].as<uint64_t>();
+        a.s0.y[j] = c0->tab[j].y[1 - par].as<uint64_t>();
+        a.s1.t[j] = c1->tab[j].t[1 - par].as<uint64_t>();
+        a.s1.y[j] = c1->tab[j].y[1 - par].as<uint64_t>();
+    }
+    a.parent_pos = S.pos[par].as<uint32_t>();
+    a.valid = c0->valid.as<uint64_t>();
+    a.C = L.C_cap;   // grid hint; the real C comes from LoopCtl
+    a.d = S.d;
+    a.nw = (uint32_t)c0->nw;
+    a.client_base = c0->client_base;
+    a.prf_seed = S.cfg->prf_seed;
+    a.level = L.lv;
+    a.n = (uint32_t)c0->n;
+    a.ctl = S.ctl.as<LoopCtl>();
+    uint64_t* part = S.partials.as<uint64_t>();
+    if (S.cfg->gc && L.pmode != 0) return level_gc_tests(S, L, a);
+    if (L.pmode == 0) {
+        HIP_TRY(c0, launch_eq_count(a, part, c0->stream));
+    } else if (L.pmode == 1) {
+        HIP_TRY(c0, launch_child_sums_fe(a, part, c0->stream, false));
+    } else {
+        HIP_TRY(c0, launch_child_sums_fe255(a, part, c0->stream));
+    }
+    return FHH_OK;
+}
+
+// cross-rank sum (client-sharded multi-GPU), and the level's record for cfg->counts
+int level_reduce(Loop& S, const Level& L) {
+    fhh_ctx* c0 = S.c0;
+    const fhh_sim_config* cfg = S.cfg;
+    // (the count is the capacity bound: entries past C are never read)
+    const uint64_t count = L.C_cap * L.per;
+    if (S.distributed) {
+        const bool timed = L.timed && cfg->comm;   // (the callback path drains the stream: nothing to time)
+        size_t ar_slot = 0;
+        if (timed) HIP_TRY(c0, timing_begin(c0, &ar_slot));
+        int rc = loop_allreduce(S, S.partials.as<uint64_t>(), S.red(), count);
+        if (rc) return rc;
+        if (timed) HIP_TRY(c0, timing_end(c0, ar_slot, kAllreduceTag));
+    }
+    if (S.record) {
+        const size_t off = S.rec_off.empty() ? 0 : S.rec_off.back() + (size_t)S.rec_stride.back();
+        const size_t need = (off + count) * 8;
+        if (S.rec.bytes < need) {
+            PinnedBuf nb;
+            HIP_TRY(c0, hipStreamSynchronize(c0->stream));
+            HIP_TRY(c0, nb.ensure(std::max(need * 2, (size_t)1 << 20)));
+            if (S.rec.p) std::memcpy(nb.p, S.rec.p, S.rec.bytes);
+            S.rec.swap(nb);
+        }
+        S.rec_off.resize(L.lv + 1);
+        S.rec_stride.resize(L.lv + 1);
+        S.rec_off[L.lv] = off;
+        S.rec_stride[L.lv] = (uint32_t)count;   // u64 words recorded for this level
+        // mode 0: counts; FE: the 4 limbs; FE255: the 16 limbs (v0 - v1 derived at the end)
+        HIP_TRY(c0, hipMemcpyAsync(S.rec.as<uint64_t>() + off, S.red(), (size_t)count * 8, hipMemcpyDeviceToHost, c0->stream));
+    }
+    return FHH_OK;
+}
+
+// leader keep decision + prune (or final list at the last level)
+int level_prune(Loop& S, const Level& L) {
+    fhh_ctx* c0 = S.c0;
+    const uint32_t d = S.d;
+    if (L.last) HIP_TRY(c0, S.final_vals.ensure((size_t)S.F_cap * 20 * 4));
+    PruneArgs pa{};
+    pa.ctl = S.ctl.as<LoopCtl>();
+    pa.partials = S.red();
+    pa.mode = L.pmode;
+    pa.d = d;
+    pa.thr = S.thr;
+    pa.thr_last = S.thr_last;
+    pa.last = L.last ? 1 : 0;
+    pa.pos_in = S.pos[L.par].as<uint32_t>();
+    pa.pos_out = S.pos[1 - L.par].as<uint32_t>();
+    for (uint32_t j = 0; j < kMaxDims; j++)
+        pa.live_out[j] = S.live[1 - L.par].as<uint32_t>() + (size_t)std::min(j, d - 1) * S.E_cap;
+    pa.mark = S.mark.as<uint32_t>();
+    pa.hist_out = S.hist_ptr[L.lv];
+    pa.sizes_out = S.sizes.as<uint32_t>() + (size_t)L.lv * (4 + kMaxDims);
+    pa.final_vals = L.last ? S.final_vals.as<uint32_t>() : nullptr;
+    pa.E_cap = S.E_cap;
+    pa.F_cap = S.F_cap;
+    pa.level = L.lv;
+    pa.nw = (uint32_t)c0->nw;
+    pa.njobs_per_ctx = d;
+    pa.nctx = 2;
+    pa.grid_waves = S.grid_waves;
+    pa.unit = (uint32_t)c0->nw;
+    pa.max_group = expand_max_group(S.variant);
+    pa.max_wpi = expand_max_wpi(S.variant);
+    pa.zero_partials = (S.cfg->mode != 0 && !L.last) ? S.partials.as<uint64_t>() : nullptr;
+    pa.ring32 = S.plan(L.pmode).ring32 ? 1u : 0u;
+    pa.zero_count = (uint64_t)L.C_cap * 4;
+    HIP_TRY(c0, launch_prune(pa, c0->stream));
+    return FHH_OK;
+}
+
+// a batch ended in an abort (h, read back at level batch_end): grow, keep what the prune of
+// h->abort_level reads; the caller resumes there
+int loop_grow(Loop& S, const LoopCtl* h, uint32_t batch_end) {
+    fhh_ctx* c0 = S.c0;
+    const uint32_t d = S.d;
+    const uint32_t la = h->abort_level;
+    const bool la_last = la + 1 == S.levels;
+    uint32_t nE = 0;
+    int rc = loop_entry_cap(S, std::max<uint32_t>(h->need_entries, 1), la, nE);
+    if (rc) return rc;
+    const uint32_t nF = std::max(S.F_cap, next_pow2(std::max<uint32_t>(h->need_nodes, 1)) * 2);
+    const uint32_t la_per = S.cfg->mode == 0 ? 1 : (la_last ? 16 : 4);
+    if (std::getenv("FHH_DEBUG_LOOP"))
+        std::fprintf(stderr, "[fhh loop] abort at level %u (batch end %u): need_entries %u need_nodes %u "
+                     "F %u C %u -> E_cap %u F_cap %u\n", la, batch_end, h->need_entries, h->need_nodes, h->F,
+                     h->C, nE, nF);
+    // the tables of parity la & 1 are rewritten by level la + 1: released first, so the
+    // peak while the preserved ones are copied is one old table, not all of them
+    for (fhh_ctx* c : S.cs)
+        for (uint32_t j = 0; j < d; j++) table_release(c->tab[j], la & 1);
+    for (fhh_ctx* c : S.cs)
+        for (uint32_t j = 0; j < d; j++) {
+            // child tables of level la (parity 1 - la&1) hold 2 * n_live(la) entries
+            rc = table_grow(c, c->tab[j], 1 - (la & 1), nE, 2 * (size_t)h->n_live[j]);
             if (rc) return rc;
-            const LoopCtl* h = B.ctl_host.as<LoopCtl>();
-            if (h->abort) {
-                // grow, keep what the prune of abort_level reads, resume there
-                const uint32_t la = h->abort_level;
-                const bool la_last = la + 1 == levels;
-                uint32_t nE = 0;
-                rc = loop_entry_cap(cs, cfg, B, d, B.E_cap, std::max<uint32_t>(h->need_entries, 1), la, nE);
-                if (rc) return rc;
-                const uint32_t nF = std::max(B.F_cap, next_pow2(std::max<uint32_t>(h->need_nodes, 1)) * 2);
-                const uint32_t la_per = cfg->mode == 0 ? 1 : (la_last ? 16 : 4);
-                if (std::getenv("FHH_DEBUG_LOOP"))
-                    std::fprintf(stderr, "[fhh loop] abort at level %u (batch end %u): need_entries %u need_nodes %u "
-                                 "F %u C %u -> E_cap %u F_cap %u\n", la, lv, h->need_entries, h->need_nodes, h->F,
-                                 h->C, nE, nF);
-                // the tables of parity la & 1 are rewritten by level la + 1: released first, so the
-                // peak while the preserved ones are copied is one old table, not all of them
-                for (fhh_ctx* c : cs)
-                    for (uint32_t j = 0; j < d; j++) table_release(c->tab[j], la & 1);
-                for (fhh_ctx* c : cs)
-                    for (uint32_t j = 0; j < d; j++) {
-                        // child tables of level la (parity 1 - la&1) hold 2 * n_live(la) entries
-                        rc = table_grow(c, c->tab[j], 1 - (la & 1), nE, 2 * (size_t)h->n_live[j]);
-                        if (rc) return rc;
-                    }
-                for (fhh_ctx* c : cs)
-                    for (uint32_t j = 0; j < d; j++) {
-                        rc = table_grow(c, c->tab[j], la & 1, nE, 0);
-                        if (rc) return rc;
-                    }
-                rc = loop_resize(c0, B, nE, nF, levels, la, true, h->F, h->C, la_per);
-                if (rc) return rc;
-                const uint32_t zero = 0;
-                HIP_TRY(c0, hipMemcpy(B.ctl.p, &zero, 4, hipMemcpyHostToDevice));   // abort = 0
-                lv = la;
-                prune_only = true;
-                (void)per_level_per;
-            }
         }
-    }
-    if (B.bot) {
-        // every instance the crawl used was waited for at its upload; lookahead ones still running
-        // are abandoned (the destructor stops the workers after their current instance)
-        std::lock_guard<std::mutex> lk(B.bot->mu);
-        c0->stats.base_ot_ms += B.bot->compute_ms;
-        c0->stats.base_ot_stall_ms += B.bot->stall_ms;
-        c0->stats.base_ot_instances += B.bot->computed;
-    }
-    c0->loop_cap_hint = std::max(B.E_cap, B.F_cap);   // the next crawl starts at this size
-    pc.mark("loop");
-    // ---- readback: sizes, hist, final values -> host-side state of both servers ----
+    for (fhh_ctx* c : S.cs)
+        for (uint32_t j = 0; j < d; j++) {
+            rc = table_grow(c, c->tab[j], la & 1, nE, 0);
+            if (rc) return rc;
+        }
+    rc = loop_resize(c0, S, nE, nF, S.levels, la, true, h->F, h->C, la_per);
+    if (rc) return rc;
+    const uint32_t zero = 0;
+    HIP_TRY(c0, hipMemcpy(S.ctl.p, &zero, 4, hipMemcpyHostToDevice));   // abort = 0
+    return FHH_OK;
+}
+
+// readback: sizes, hist, final values, frontier -> host-side state and stats of both servers; sz = the
+// levels' size rows [levels][4 + kMaxDims] (C, kept, -, -, n_live per dim)
+int loop_readback(Loop& S, std::vector<uint32_t>& sz) {
+    fhh_ctx* c0 = S.c0;
+    const fhh_sim_config* cfg = S.cfg;
+    const uint32_t d = S.d, levels = S.levels;
     // every level's hist row is packed on the device (k_gather_hist) and copied in one transfer
-    const uint64_t hist_cap = (uint64_t)levels * B.F_cap;
-    HIP_TRY(c0, B.hist_rows.ensure((size_t)levels * sizeof(uint32_t*)));
-    HIP_TRY(c0, B.hist_packed.ensure(hist_cap * 4));
-    HIP_TRY(c0, hipMemcpyAsync(B.hist_rows.p, B.hist_ptr.data(), (size_t)levels * sizeof(uint32_t*),
+    const uint64_t hist_cap = (uint64_t)levels * S.F_cap;
+    HIP_TRY(c0, S.hist_rows.ensure((size_t)levels * sizeof(uint32_t*)));
+    HIP_TRY(c0, S.hist_packed.ensure(hist_cap * 4));
+    HIP_TRY(c0, hipMemcpyAsync(S.hist_rows.p, S.hist_ptr.data(), (size_t)levels * sizeof(uint32_t*),
                                hipMemcpyHostToDevice, c0->stream));
-    HIP_TRY(c0, launch_gather_hist(B.sizes.as<uint32_t>(), 4 + kMaxDims, B.hist_rows.as<const uint32_t*>(), levels,
-                                   B.hist_packed.as<uint32_t>(), hist_cap, c0->stream));
+    HIP_TRY(c0, launch_gather_hist(S.sizes.as<uint32_t>(), 4 + kMaxDims, S.hist_rows.as<const uint32_t*>(), levels,
+                                   S.hist_packed.as<uint32_t>(), hist_cap, c0->stream));
     // (the engine stream is non-blocking: plain hipMemcpy would not wait for k_gather_hist)
-    std::vector<uint32_t> sz((size_t)levels * (4 + kMaxDims));
-    HIP_TRY(c0, hipMemcpyAsync(sz.data(), B.sizes.p, sz.size() * 4, hipMemcpyDeviceToHost, c0->stream));
+    sz.resize((size_t)levels * (4 + kMaxDims));
+    HIP_TRY(c0, hipMemcpyAsync(sz.data(), S.sizes.p, sz.size() * 4, hipMemcpyDeviceToHost, c0->stream));
     HIP_TRY(c0, hipStreamSynchronize(c0->stream));
     uint64_t hist_total = 0;
     for (uint32_t lv = 0; lv < levels; lv++) hist_total += sz[(size_t)lv * (4 + kMaxDims) + 1];
     if (hist_total > hist_cap) return c0->fail(FHH_E_STATE, "loop: kept-children lists exceed their capacity");
     std::vector<uint32_t> packed(hist_total);
     if (hist_total) {
-        HIP_TRY(c0, hipMemcpyAsync(packed.data(), B.hist_packed.p, hist_total * 4, hipMemcpyDeviceToHost, c0->stream));
+        HIP_TRY(c0, hipMemcpyAsync(packed.data(), S.hist_packed.p, hist_total * 4, hipMemcpyDeviceToHost, c0->stream));
         HIP_TRY(c0, hipStreamSynchronize(c0->stream));
     }
     std::vector<std::vector<std::pair<uint32_t, uint32_t>>> hist(levels);
@@ -1721,22 +1749,26 @@ int sim_crawl_device_loop(fhh_ctx* c0, fhh_ctx* c1, const fhh_sim_config* cfg, u
     }
     const uint32_t nfin = sz[(size_t)(levels - 1) * (4 + kMaxDims) + 1];
     std::vector<uint32_t> fv((size_t)nfin * 20);
-    if (nfin) HIP_TRY(c0, hipMemcpy(fv.data(), B.final_vals.p, fv.size() * 4, hipMemcpyDeviceToHost));
+    if (nfin) HIP_TRY(c0, hipMemcpy(fv.data(), S.final_vals.p, fv.size() * 4, hipMemcpyDeviceToHost));
     // frontier before the last crawl: depth levels-1, states in table buffer (levels-1)&1
     const int fpar = (levels - 1) & 1;
     const uint32_t Ffront = levels >= 2 ? sz[(size_t)(levels - 2) * (4 + kMaxDims) + 1] : 1;
     std::vector<uint32_t> fpos((size_t)Ffront * d);
-    if (Ffront) HIP_TRY(c0, hipMemcpy(fpos.data(), B.pos[fpar].p, fpos.size() * 4, hipMemcpyDeviceToHost));
+    if (Ffront) HIP_TRY(c0, hipMemcpy(fpos.data(), S.pos[fpar].p, fpos.size() * 4, hipMemcpyDeviceToHost));
     std::vector<std::vector<uint32_t>> flive(d);
     for (uint32_t j = 0; j < d; j++) {
         const uint32_t nl = levels >= 2 ? sz[(size_t)(levels - 2) * (4 + kMaxDims) + 4 + j] : 1;
         flive[j].resize(nl);
         if (nl)
-            HIP_TRY(c0, hipMemcpy(flive[j].data(), B.live[fpar].as<uint32_t>() + (size_t)j * B.E_cap, (size_t)nl * 4,
+            HIP_TRY(c0, hipMemcpy(flive[j].data(), S.live[fpar].as<uint32_t>() + (size_t)j * S.E_cap, (size_t)nl * 4,
                                   hipMemcpyDeviceToHost));
     }
+    // entries k_expand read per level: the dims' live entries of the level before (the roots at level 0)
+    std::vector<uint64_t> live_sum(levels, 0);
+    for (uint32_t lv = 0; lv < levels; lv++)
+        for (uint32_t j = 0; j < d; j++) live_sum[lv] += lv == 0 ? 1 : sz[(size_t)(lv - 1) * (4 + kMaxDims) + 4 + j];
     for (int s = 0; s < 2; s++) {
-        fhh_ctx* c = cs[s];
+        fhh_ctx* c = S.cs[s];
         c->hist.assign(hist.begin(), hist.begin() + (levels - 1));
         c->last_hist = c->hist;
         c->last_depth = levels;
@@ -1758,38 +1790,34 @@ int sim_crawl_device_loop(fhh_ctx* c0, fhh_ctx* c1, const fhh_sim_config* cfg, u
         c->pending_C = 0;
         c->phase = Phase::kFrontier;   // after tree_prune_last (collect.rs:931-942)
         for (uint32_t lv = 0; lv < levels; lv++) {
-            const uint32_t* row = &sz[(size_t)lv * (4 + kMaxDims)];
-            uint64_t live_sum = 0;
-            for (uint32_t j = 0; j < d; j++) live_sum += lv == 0 ? 1 : sz[(size_t)(lv - 1) * (4 + kMaxDims) + 4 + j];
-            c->stats.aes_blocks += live_sum * 4 * c->n;
-            c->stats.ref_evals += (uint64_t)row[0] * c->n * 2 * d;
+            c->stats.aes_blocks += live_sum[lv] * 4 * c->n;
+            c->stats.ref_evals += (uint64_t)sz[(size_t)lv * (4 + kMaxDims)] * c->n * 2 * d;
             c->stats.levels += 1;
         }
     }
     // expand_blocks_timed for c0's timed launches: both servers
-    {
-        uint64_t blocks = 0;
-        for (uint32_t lv = 0; lv < levels; lv++) {
-            uint64_t live_sum = 0;
-            for (uint32_t j = 0; j < d; j++) live_sum += lv == 0 ? 1 : sz[(size_t)(lv - 1) * (4 + kMaxDims) + 4 + j];
-            if (lv % c0->timing_every == 0) blocks += live_sum * 4 * c0->n * 2;
-        }
-        if (c0->timing) c0->stats.expand_blocks_timed += blocks;
-    }
-    // optional per-level records
+    for (uint32_t lv = 0; lv < levels && c0->timing; lv++)
+        if (lv % c0->timing_every == 0) c0->stats.expand_blocks_timed += live_sum[lv] * 4 * c0->n * 2;
+    return FHH_OK;
+}
+
+// optional per-level records: cfg->level_children / level_kept / counts
+void loop_records(const Loop& S, const std::vector<uint32_t>& sz) {
+    const fhh_sim_config* cfg = S.cfg;
+    const bool ring32 = S.plan(1).ring32;   // r06: the FE levels' shares are Z_2^32's
     uint64_t off = 0;
-    for (uint32_t lv = 0; lv < levels; lv++) {
+    for (uint32_t lv = 0; lv < S.levels; lv++) {
         const uint32_t C = sz[(size_t)lv * (4 + kMaxDims)];
         if (cfg->level_children) cfg->level_children[lv] = C;
         if (cfg->level_kept) cfg->level_kept[lv] = sz[(size_t)lv * (4 + kMaxDims) + 1];
-        if (record && lv < B.rec_off.size()) {
-            const uint64_t* r = B.rec.as<uint64_t>() + B.rec_off[lv];
-            const bool lvl_last = lv + 1 == levels;
+        if (S.record && lv < S.rec_off.size()) {
+            const uint64_t* r = S.rec.as<uint64_t>() + S.rec_off[lv];
+            const bool lvl_last = lv + 1 == S.levels;
             for (uint32_t c = 0; c < C && off + c < cfg->counts_capacity; c++) {
                 uint64_t v;
                 if (cfg->mode == 0) {
                     v = r[c];
-                } else if (!lvl_last && ring32) {   // r06: Z_2^32 shares
+                } else if (!lvl_last && ring32) {
                     v = (uint32_t)(r[c * 4] - r[c * 4 + 2]);
                 } else if (!lvl_last) {
                     v = fe_sub_canon(fe_canon_from_limbs(r[c * 4], r[c * 4 + 1]), fe_canon_from_limbs(r[c * 4 + 2], r[c * 4 + 3]));
@@ -1803,25 +1831,82 @@ int sim_crawl_device_loop(fhh_ctx* c0, fhh_ctx* c1, const fhh_sim_config* cfg, u
         }
         off += C;
     }
-    if (cfg->probe_n_levels) {
-        std::vector<uint32_t> pC(cfg->probe_n_levels);
-        HIP_TRY(c0, hipMemcpy(pC.data(), B.probe_C.p, pC.size() * 4, hipMemcpyDeviceToHost));
-        const size_t row = (size_t)cfg->probe_n_clients * d * 2;   // states per (server, child)
-        const size_t cap = cfg->probe_capacity;
-        for (uint32_t k = 0; k < cfg->probe_n_levels; k++) {
-            cfg->probe_children[k] = pC[k];
-            const size_t nc = std::min<size_t>(std::min<size_t>(pC[k], cap), B.probe_stride[k]);
-            if (!nc || !B.probe_seed[k].p) continue;
-            for (int s = 0; s < 2; s++) {
-                uint8_t* hs = cfg->probe_seeds + (((size_t)k * 2 + s) * cap) * row * 16;
-                uint8_t* ht = cfg->probe_ty + (((size_t)k * 2 + s) * cap) * row;
-                HIP_TRY(c0, hipMemcpy(hs, B.probe_seed[k].as<uint8_t>() + (size_t)s * B.probe_stride[k] * row * 16,
-                                      nc * row * 16, hipMemcpyDeviceToHost));
-                HIP_TRY(c0, hipMemcpy(ht, B.probe_ty[k].as<uint8_t>() + (size_t)s * B.probe_stride[k] * row, nc * row,
-                                      hipMemcpyDeviceToHost));
+}
+
+// the parity probe's captured states -> cfg->probe_children / probe_seeds / probe_ty
+int loop_probe_readback(Loop& S) {
+    fhh_ctx* c0 = S.c0;
+    const fhh_sim_config* cfg = S.cfg;
+    if (!cfg->probe_n_levels) return FHH_OK;
+    std::vector<uint32_t> pC(cfg->probe_n_levels);
+    HIP_TRY(c0, hipMemcpy(pC.data(), S.probe_C.p, pC.size() * 4, hipMemcpyDeviceToHost));
+    const size_t row = (size_t)cfg->probe_n_clients * S.d * 2;   // states per (server, child)
+    const size_t cap = cfg->probe_capacity;
+    for (uint32_t k = 0; k < cfg->probe_n_levels; k++) {
+        cfg->probe_children[k] = pC[k];
+        const size_t nc = std::min<size_t>(std::min<size_t>(pC[k], cap), S.probe_stride[k]);
+        if (!nc || !S.probe_seed[k].p) continue;
+        for (int s = 0; s < 2; s++) {
+            uint8_t* hs = cfg->probe_seeds + (((size_t)k * 2 + s) * cap) * row * 16;
+            uint8_t* ht = cfg->probe_ty + (((size_t)k * 2 + s) * cap) * row;
+            HIP_TRY(c0, hipMemcpy(hs, S.probe_seed[k].as<uint8_t>() + (size_t)s * S.probe_stride[k] * row * 16,
+                                  nc * row * 16, hipMemcpyDeviceToHost));
+            HIP_TRY(c0, hipMemcpy(ht, S.probe_ty[k].as<uint8_t>() + (size_t)s * S.probe_stride[k] * row, nc * row,
+                                  hipMemcpyDeviceToHost));
+        }
+    }
+    return FHH_OK;
+}
+
+// The whole crawl enqueued without host round trips: every kBatch levels (and at the end) LoopCtl comes
+// back; after an abort the buffers grow and the crawl resumes at the prune of the level that aborted.
+int sim_crawl_device_loop(fhh_ctx* c0, fhh_ctx* c1, const fhh_sim_config* cfg, uint32_t levels, uint64_t thr,
+                          uint32_t thr_last) {
+    PhaseClock pc;
+    Loop S(c0, c1, cfg, levels, thr, thr_last);
+    int rc = loop_setup(S);
+    if (rc) return rc;
+    pc.mark("setup");
+    const uint32_t kBatch = 32;
+    bool prune_only = false;           // resume after growth: prune of this level only
+    for (uint32_t lv = 0; lv < levels;) {
+        const Level L(S, lv);
+        if (!prune_only) {
+            if ((rc = level_expand(S, L)) || (rc = level_tests(S, L)) || (rc = level_reduce(S, L))) return rc;
+        }
+        prune_only = false;
+        rc = level_prune(S, L);
+        if (rc) return rc;
+        lv++;
+        if (lv % kBatch == 0 || lv == levels) {
+            HIP_TRY(c0, hipMemcpyAsync(S.ctl_host.p, S.ctl.p, sizeof(LoopCtl), hipMemcpyDeviceToHost, c0->stream));
+            rc = sync(c0);
+            if (rc) return rc;
+            const LoopCtl* h = S.ctl_host.as<LoopCtl>();
+            if (h->abort) {
+                rc = loop_grow(S, h, lv);
+                if (rc) return rc;
+                lv = h->abort_level;
+                prune_only = true;
             }
         }
     }
+    if (S.bot) {
+        // every instance the crawl used was waited for at its upload; lookahead ones still running
+        // are abandoned (the destructor stops the workers after their current instance)
+        std::lock_guard<std::mutex> lk(S.bot->mu);
+        c0->stats.base_ot_ms += S.bot->compute_ms;
+        c0->stats.base_ot_stall_ms += S.bot->stall_ms;
+        c0->stats.base_ot_instances += S.bot->computed;
+    }
+    c0->loop_cap_hint = std::max(S.E_cap, S.F_cap);   // the next crawl starts at this size
+    pc.mark("loop");
+    std::vector<uint32_t> sz;
+    rc = loop_readback(S, sz);
+    if (rc) return rc;
+    loop_records(S, sz);
+    rc = loop_probe_readback(S);
+    if (rc) return rc;
     pc.mark("readback");
     return FHH_OK;
 }

@@ -18,6 +18,8 @@
 #include <string>
 #include <vector>
 
+#include "gt_plan.h"
+
 struct fhh_comm;   // include/fhh.h (fhh_comm.cpp)
 
 namespace fhh {
@@ -251,10 +253,7 @@ struct GcArgs {
     // Without lab_tm (bits = 3, 4: k_gt_garble_r32 / k_gt_eval_r32) sh_gb / sh_ev hold u32 values [G N] too
     uint32_t ring32;
 };
-constexpr int kGtMaxBits = 4;   // 16 rows (d = 2); wider tests keep the half-gates chain
-constexpr int kGtTmMaxBits = 4;   // the table kernels read the tile-major labels (lab_tm) for b <= 4 (d <= 2)
-constexpr int kGtTmPadBits = 2;   // b <= 2 (d = 1): plane rows padded to whole 512-client tiles (nw % 8 == 0);
-                                  // b = 3, 4 keep Npad = 64 nw, so their OT indices and the wire stay as they were
+// (kGtMaxBits, kGtTmMaxBits, kGtTmPadBits: gt_plan.h)
 
 struct PruneArgs {
     LoopCtl* ctl;

@@ -65,6 +65,43 @@ def test_device_loop_large_with_growth(oracle, variant):
     assert seeds.shape[0] == int(dev.level_kept[-2])
 
 
+# (d, gc, Z_2^32 shares, table_row_major, the form's bytes per test at the FE levels: csrc/gt_plan.h)
+GC_FORMS = [
+    (1, "ideal", False, False, 402),        # ideal-OT circuit
+    (1, "ot-circuit", False, False, 402),   # the circuit with label shares where the table exists
+    (1, "ot", False, False, 150),           # tile-major table on whole 512-client tiles
+    (1, "ot", True, False, 150),            # ... in Z_2^32
+    (2, "ot", False, False, 320),           # tile-major table on windows
+    (2, "ot", True, False, 320),
+    (2, "ot", False, True, 802),            # row-major table
+    (2, "ot", True, True, 802),             # ... in Z_2^32 (k_ring32_child_partials)
+    (3, "ot", False, False, 1202),          # no table at 2d = 6: the circuit with label shares
+]
+
+
+@pytest.mark.parametrize("d,gc,ring,row_major,per_test", GC_FORMS,
+                         ids=[f"d{f[0]}-{f[1]}" + ("-ring32" if f[2] else "") + ("-row-major" if f[3] else "")
+                              for f in GC_FORMS])
+def test_device_loop_gc_forms_in_chunks_with_growth(monkeypatch, capfd, d, gc, ring, row_major, per_test):
+    """Every form the level loop's equality test takes, with 3 children per GC + OT chunk (the levels' capacity
+    is a power of two: the last chunk is partial) and a growth abort in the same crawl: 200 clients (nw = 4, no
+    multiple of 8), 8 levels, fresh collections that start at capacity 2 and reach 5 nodes. The FieldElm level
+    runs the circuit + share OT in every case. Same signature as the plain FE crawl, run afterwards."""
+    from fuzzyheavyhitters_amd import sim_crawl, workload
+    wl = workload.zipf_workload(200, 32, d, num_sites=6, seed=7)
+    c0, c1 = _pair(wl.left[:, :, :8].copy(), wl.right[:, :, :8].copy(), wl.root_seeds)
+    for c in (c0, c1):
+        c.set_table_row_major(row_major)
+    monkeypatch.setenv("FHH_GC_CHUNK_BYTES", str(3 * per_test * 256))
+    monkeypatch.setenv("FHH_DEBUG_LOOP", "1")
+    capfd.readouterr()
+    got = sim_crawl(c0, c1, 0.05, mode="fe", prf_seed=9, gc=gc, init_capacity=2, table_ring32=ring)
+    assert "[fhh loop] abort at level" in capfd.readouterr().err   # the crawl grew and resumed
+    plain = sim_crawl(c0, c1, 0.05, mode="fe", prf_seed=9)
+    assert _sig(got) == _sig(plain)
+    assert max(plain.level_children) > 6 and len(got.final) > 0
+
+
 def test_device_loop_d2_coords(oracle):
     from fuzzyheavyhitters_amd import sim_crawl, workload
     wl = workload.coords_workload(1500, ball_size=3, num_centroids=40, side_km=4.0)

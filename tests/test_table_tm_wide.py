@@ -64,6 +64,20 @@ def test_gt_window_host(tmp_path):
     assert out.returncode == 0 and out.stdout.strip() == "OK", out.stdout + out.stderr
 
 
+def test_gt_plan_host(tmp_path):
+    """csrc/gt_plan.h on the host (tests/host/gt_plan_host_test.cpp): the form of the equality test for every
+    caller, GC form, level kind, d = 1 .. 4, ring request, table_row_major and nw = 1 .. 16 384 against the literal
+    table of what the level loop, gt_cot_host and party_begin decided before the header existed; the chunk-sizing
+    estimates 402 and 320 that the chunked loop tests use; the party ABI row-major and unfused at b = 3, 4."""
+    if not shutil.which("hipcc"):
+        pytest.skip("hipcc not available")
+    exe = tmp_path / "gt_plan_host"
+    subprocess.run(["hipcc", "--offload-arch=gfx950", "-O1", "-std=c++17", "-Wall",
+                    os.path.join(ROOT, "tests", "host", "gt_plan_host_test.cpp"), "-o", str(exe)], check=True)
+    out = subprocess.run([str(exe)], capture_output=True, text=True)
+    assert out.returncode == 0 and out.stdout.startswith("OK "), out.stdout + out.stderr
+
+
 def test_set_table_row_major_abi():
     """The switch exists, refuses a NULL ctx and values other than 0 / 1."""
     from fuzzyheavyhitters_amd._lib import lib
