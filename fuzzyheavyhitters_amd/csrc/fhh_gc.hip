@@ -906,11 +906,18 @@ __device__ __forceinline__ void gt_tile_rows(const GcArgs& a, uint64_t g, uint32
 #pragma unroll
     for (int i = 0; i < 32; i++) x[i] = __builtin_nontemporal_load(t0 + (32 * rg + i) * 16);
     if constexpr (B == 2) {
+        // both tiles' 64 words are in flight before the first XOR (folded load by load, the garbler's register
+        // pressure made the compiler reuse one temporary and wait for bit 1's loads one at a time, ~10 memory
+        // round trips per tile where this is one); the fence holds the order
         const uint32_t* t1 = t0 + (uint64_t)Npt * kGtTileWords;   // bit 1's tile
-        const uint32_t y0 = __builtin_nontemporal_load(t1 + (rg ? 32 * rg - 1 : 127) * 16);
-        x[0] ^= y0;
+        uint32_t y[32];
+        y[0] = __builtin_nontemporal_load(t1 + (rg ? 32 * rg - 1 : 127) * 16);
 #pragma unroll
-        for (int i = 1; i < 32; i++) x[i] ^= __builtin_nontemporal_load(t1 + (32 * rg + i - 1) * 16);
+        for (int i = 1; i < 32; i++) y[i] = __builtin_nontemporal_load(t1 + (32 * rg + i - 1) * 16);
+        __builtin_amdgcn_sched_barrier(0);
+        const uint32_t y0 = y[0];
+#pragma unroll
+        for (int i = 0; i < 32; i++) x[i] ^= y[i];
         if (rg == 0) {   // e_1's row 127: the reduction into rows 1, 2, 7 (row 0 took it above)
             x[1] ^= y0;
             x[2] ^= y0;
@@ -1064,9 +1071,8 @@ __global__ __launch_bounds__(kGcThreads) void k_gt_garble_tm(GcArgs a) {
     static_assert(B <= kGtTmMaxBits, "the tile-major garbler takes b <= 4");
     __shared__ uint32_t tbl_gc[GcTab::kWords];
     __shared__ __attribute__((aligned(16))) uint32_t stage[kGtWaves][512];
-    // (b = 3, 4: the wave index as a scalar, so the tile's index arithmetic stays out of the VGPRs)
-    const uint32_t lane = threadIdx.x & 63,
-                   wv = B > kGtTmPadBits ? (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) : threadIdx.x >> 6;
+    // (the wave index as a scalar, so the tile's index arithmetic stays out of the VGPRs)
+    const uint32_t lane = threadIdx.x & 63, wv = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const uint64_t n_act = gc_active(a);
     const uint32_t Npt = (B > kGtTmPadBits ? a.nw + 7 : a.nw) / 8;   // 512-test tiles (b > 2: windows) per group
     const uint64_t tiles = (n_act / a.N) * Npt;
@@ -1272,9 +1278,8 @@ __global__ __launch_bounds__(kGcThreads) void k_gt_eval_tm(GcArgs a) {
     static_assert(B <= kGtTmMaxBits, "the tile-major evaluator takes b <= 4");
     __shared__ uint32_t tbl_gc[GcTab::kWords];
     __shared__ __attribute__((aligned(16))) uint32_t stage[kGtWaves][512];
-    // (b = 3, 4: the wave index as a scalar, so the tile's index arithmetic stays out of the VGPRs)
-    const uint32_t lane = threadIdx.x & 63,
-                   wv = B > kGtTmPadBits ? (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) : threadIdx.x >> 6;
+    // (the wave index as a scalar, so the tile's index arithmetic stays out of the VGPRs)
+    const uint32_t lane = threadIdx.x & 63, wv = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const uint64_t n_act = gc_active(a);
     const uint32_t Npt = (B > kGtTmPadBits ? a.nw + 7 : a.nw) / 8;
     const uint64_t tiles = (n_act / a.N) * Npt;
@@ -1314,8 +1319,41 @@ __global__ __launch_bounds__(kGcThreads) void k_gt_eval_tm(GcArgs a) {
         const uint32_t nod[B][4] = {};
         gt_tile_keys<B, false>(a, g, iw, Npt, stage[wv], lane, nod, S, col, xcol);
         uint64_t acc_lo = 0, acc_hi = 0;
-#pragma unroll 1
-        for (int r = 0; r < 4; r++) {   // round r's 2 tests: 2 AES blocks in lockstep (4 spilled 6 VGPRs)
+        // The tile's 8 row messages gt_msgs[(row - 1) n + t] are all in flight before round 0's AES (row and t
+        // are known once the keys are dealt): loaded where they are used, each cost its wave a memory round
+        // trip of its own, 8 per tile, with the lookup stream of its SIMD a wave short meanwhile. A test
+        // without a message (row 0, whose index would wrap, or a dead test of a tail tile, whose index lies
+        // past the buffer) loads element 0 instead and never uses it: unconditional loads go out as one batch,
+        // predicated ones each wait in a branch of their own. m rotates by one round with S.
+        // b <= 2 only. At b = 3, 4 the messages are still loaded where they are used: there the window's fold
+        // (gt_window_fold) pays several times these round trips, and with 16 more registers live in the rounds
+        // the compiler broke the b = 4 fold's batches into twice as many waits (profiles/gt_msg_batch/).
+        constexpr bool EARLY = B <= kGtTmPadBits;
+        uint64_t m[8] = {};
+        if constexpr (EARLY) {
+            uint64_t at[8];
+#pragma unroll
+            for (int j = 0; j < 8; j++) {
+                const uint32_t i = 512 * iw + gt_tile_test(lane, j >> 1, j & 1);
+                const uint32_t row = (col >> (4 * j)) & 0xFu;
+                at[j] = row != 0 && i < a.N ? (uint64_t)(row - 1) * n + g * a.N + i : 0;
+            }
+            if (a.ring32) {
+#pragma unroll
+                for (int j = 0; j < 8; j++) {
+                    // (a zero of its own for each high half: sharing one zero register, a message was loaded into
+                    // that register's pair and copied out of it at once, behind a wait for the load)
+                    uint32_t z = 0;
+                    asm volatile("" : "+v"(z));
+                    m[j] = reinterpret_cast<const uint32_t*>(a.gt_msgs)[at[j]] | ((uint64_t)z << 32);
+                }
+            } else {
+#pragma unroll
+                for (int j = 0; j < 8; j++) m[j] = a.gt_msgs[at[j]];
+            }
+        }
+        // round r's 2 tests: 2 AES blocks in lockstep (4 spilled 6 VGPRs)
+        auto round = [&](int r) __attribute__((always_inline)) {
             uint32_t h[2][4];
 #pragma unroll
             for (int u = 0; u < 2; u++) {
@@ -1327,8 +1365,18 @@ __global__ __launch_bounds__(kGcThreads) void k_gt_eval_tm(GcArgs a) {
                 h[u][3] = S[u][3];
             }
             aes0_mmo_tab<DevOpsX, GcTab, 2>(h, tbl_gc, b0, b1);
-            // (the row messages are loaded after the AES: r05 measured the early load neutral,
-            // profiles/r05/table/ab_gt_eval_msg.json)
+            // this round's messages are taken, and m rotated, after the AES and before the round's stores: the wait
+            // for the loads, all of it in round 0, then has no store of this tile in front of it. (The empty asm
+            // pins the rotation's copies there, behind the hash: left alone they stand where the rounds' loop is
+            // entered, and the wait with them.)
+            const uint64_t mr[2] = {m[0], m[1]};
+            if constexpr (EARLY) {
+#pragma unroll
+                for (int jj = 0; jj < 6; jj++) {
+                    m[jj] = m[jj + 2];
+                    asm volatile("" : "+v"(m[jj]) : "v"(h[0][0]));
+                }
+            }
 #pragma unroll
             for (int u = 0; u < 2; u++) {
                 const uint32_t i = 512 * iw + gt_tile_test(lane, r, u);
@@ -1338,9 +1386,11 @@ __global__ __launch_bounds__(kGcThreads) void k_gt_eval_tm(GcArgs a) {
                 const uint64_t hl = (uint64_t)h[u][0] | ((uint64_t)h[u][1] << 32);
                 uint64_t val;
                 if (a.ring32)   // r06: Z_2^32 shares, 4-B messages
-                    val = row ? (h[u][0] ^ reinterpret_cast<const uint32_t*>(a.gt_msgs)[(uint64_t)(row - 1) * n + t]) : h[u][0];
+                    val = row ? (h[u][0] ^ (EARLY ? (uint32_t)mr[u]
+                                                  : reinterpret_cast<const uint32_t*>(a.gt_msgs)[(uint64_t)(row - 1) * n + t]))
+                              : h[u][0];
                 else
-                    val = row ? (hl ^ a.gt_msgs[(uint64_t)(row - 1) * n + t])
+                    val = row ? (hl ^ (EARLY ? mr[u] : a.gt_msgs[(uint64_t)(row - 1) * n + t]))
                               : ot_fe_of_u128(hl, (uint64_t)h[u][2] | ((uint64_t)h[u][3] << 32));
                 if (a.node_partials) {
                     acc_lo += val & 0xFFFFFFFFull;
@@ -1354,7 +1404,13 @@ __global__ __launch_bounds__(kGcThreads) void k_gt_eval_tm(GcArgs a) {
 #pragma unroll
                 for (int c = 0; c < 4; c++) S[jj][c] = S[jj + 2][c];
             col >>= 8;
-        }
+        };
+        // Round 0 stands outside the loop of the others. A loop that uses loaded registers and loads nothing
+        // itself gets the wait for all loads in front of it from the compiler: with round 0 inside, that is
+        // in front of the first AES, and the messages' round trip is not overlapped at all.
+        if constexpr (EARLY) round(0);
+#pragma unroll 1
+        for (int r = EARLY ? 1 : 0; r < 4; r++) round(r);
         if (a.node_partials) gt_add_partials(a.node_partials, a.node_off + a.g_off + g, 2, acc_lo, acc_hi, lane);
     }
 }

@@ -48,6 +48,34 @@ typedef uint32_t v4u32_t __attribute__((ext_vector_type(4)));
 using ExpandTab = Tab4T32<DevOpsX>;
 constexpr int kExpandBlock = 1024;   // threads per workgroup: 16 waves share the 128 KiB of tables
 
+// The entry loop's load and store order (A/B knobs, honoured like the others only in an explicit A/B build;
+// DESIGN.md §5, profiles/gt_msg_batch/):
+//   FHH_EXPAND_SLOAD     the wave-uniform words (live[], the parent t / y words, the item's cw_bits) are read
+//                        through the scalar path, live[] one entry ahead: nothing in this launch writes them
+//                        (an earlier launch's k_prune / k_expand did)
+//   FHH_EXPAND_PREFETCH  entry e + 1's parent seeds and t / y words are requested after entry e's AES and before
+//                        its stores (nothing is held across the AES): the wait at the loop's top then leaves the
+//                        stores outstanding; as vmcnt counts loads and stores in one in-order counter, a load
+//                        issued after them waits for their retirement too
+// (One store from 8 lanes for the entry's 8 child t / y words, instead of 8 lane-0 stores, measured +2.8 % on its
+// own and nothing on top of the two above: not kept, profiles/AB_HISTORY.md.)
+#ifndef FHH_EXPAND_SLOAD
+#define FHH_EXPAND_SLOAD 1
+#endif
+#ifndef FHH_EXPAND_PREFETCH
+#define FHH_EXPAND_PREFETCH 1
+#endif
+
+// p[i] for a wave-uniform i, of words no kernel of this launch writes: a scalar load (constant address space)
+template <typename T>
+__device__ __forceinline__ T uniform_load(const T* p, size_t i) {
+#if FHH_EXPAND_SLOAD
+    return ((const __attribute__((address_space(4))) T*)p)[i];
+#else
+    return p[i];
+#endif
+}
+
 // Word w (clients 64 w .. 64 w + 63) of entries [e_begin, e_end) of job J.
 // Child seeds are written with the nontemporal hint: they are read again only at the next level,
 // and 1.3 GB per launch left dirty in L2 costs a writeback at every kernel boundary.
@@ -57,8 +85,10 @@ constexpr int kExpandBlock = 1024;   // threads per workgroup: 16 waves share th
 template <bool PAIR, bool NTL>
 __device__ __forceinline__ void expand_word(const ExpandJob& J, uint32_t w, uint32_t e_begin, uint32_t e_end,
                                             const uint32_t* tbl, uint32_t lane, uint32_t b0, uint32_t b1) {
+    constexpr bool kPrefetch = FHH_EXPAND_PREFETCH, kAhead = FHH_EXPAND_SLOAD || FHH_EXPAND_PREFETCH;
     const uint32_t c = w * 64 + lane;
     const size_t npad = J.npad, nw = J.nw;
+    if (e_begin >= e_end) return;
 
     // CorWord for (level, dim, side) — ibDCF.rs:215-217 `cor_words[state.level]`
     const size_t krow = (size_t)J.level * J.K + 2 * J.dim;
@@ -68,27 +98,44 @@ __device__ __forceinline__ void expand_word(const ExpandJob& J, uint32_t w, uint
     for (int s = 0; s < 2; s++) {
         cw[s] = J.cw_seed[(krow + s) * npad + c];
 #pragma unroll
-        for (int b = 0; b < 4; b++) cwp[s][b] = J.cw_bits[((krow + s) * 4 + b) * nw + w];
+        for (int b = 0; b < 4; b++) cwp[s][b] = uniform_load(J.cw_bits, ((krow + s) * 4 + b) * nw + w);
     }
 
-    for (uint32_t e = e_begin; e < e_end; e++) {
-        const uint32_t src = J.live[e];
-        uint32_t blk[4][4];     // index s * 2 + dir
-        uint64_t tw[2], yw[2];
-        uint64_t pb[4], py[4];  // PRG control bits (tau.bits / tau.y_bits) as ballot planes
+    uint4 sd[2];   // the entry's parent seeds and t / y words
+    uint64_t tw[2], yw[2];
+    auto fetch = [&](uint32_t src) __attribute__((always_inline)) {
 #pragma unroll
         for (int s = 0; s < 2; s++) {
-            uint4 sd;
             if constexpr (NTL) {
                 const v4u32_t v = __builtin_nontemporal_load(
                     reinterpret_cast<const v4u32_t*>(J.src_seed + ((size_t)src * 2 + s) * npad + c));
-                sd = make_uint4(v[0], v[1], v[2], v[3]);
+                sd[s] = make_uint4(v[0], v[1], v[2], v[3]);
             } else {
-                sd = J.src_seed[((size_t)src * 2 + s) * npad + c];
+                sd[s] = J.src_seed[((size_t)src * 2 + s) * npad + c];
             }
-            tw[s] = J.src_t[((size_t)src * 2 + s) * nw + w];
-            yw[s] = J.src_y[((size_t)src * 2 + s) * nw + w];
-            const uint32_t sw[4] = {sd.x, sd.y, sd.z, sd.w};
+            tw[s] = uniform_load(J.src_t, ((size_t)src * 2 + s) * nw + w);
+            yw[s] = uniform_load(J.src_y, ((size_t)src * 2 + s) * nw + w);
+        }
+    };
+    // (nothing reads live[] at or beyond e_end <= n_live)
+    uint32_t src = kAhead ? uniform_load(J.live, e_begin) : 0u;
+    if constexpr (kPrefetch) {
+        fetch(src);
+        // (the CorWord loads are waited for here, once per word: still pending at the loop's head, they cost every
+        // entry a wait for all loads at their use behind the AES, the next entry's request included)
+        asm volatile("" ::"v"(cw[0].x), "v"(cw[1].x));
+    }
+
+    for (uint32_t e = e_begin; e < e_end; e++) {
+        if constexpr (!kAhead) src = J.live[e];
+        if constexpr (!kPrefetch) fetch(src);
+        const bool more = e + 1 < e_end;   // wave-uniform
+        if (kAhead && more) src = uniform_load(J.live, e + 1);
+        uint32_t blk[4][4];     // index s * 2 + dir
+        uint64_t pb[4], py[4];  // PRG control bits (tau.bits / tau.y_bits) as ballot planes
+#pragma unroll
+        for (int s = 0; s < 2; s++) {
+            const uint32_t sw[4] = {sd[s].x, sd[s].y, sd[s].z, sd[s].w};
 #pragma unroll
             for (int dir = 0; dir < 2; dir++) {
                 prg_ctr(sw, dir, blk[s * 2 + dir]);
@@ -102,24 +149,38 @@ __device__ __forceinline__ void expand_word(const ExpandJob& J, uint32_t w, uint
         if constexpr (PAIR) aes0_mmo_pair<DevOpsX, ExpandTab, 4>(blk, tbl, b0, b1);
         else aes0_mmo_tab<DevOpsX, ExpandTab, 4>(blk, tbl, b0, b1);
 
+        // child row de = (2 e + dir) 2 + s = 4 e + q, q = 2 dir + s
+        v4u32_t out[4];
+        uint64_t tq[4], yq[4];
 #pragma unroll
         for (int s = 0; s < 2; s++) {
             const uint32_t tmask = 0u - (uint32_t)((tw[s] >> lane) & 1);   // if state.bit
 #pragma unroll
             for (int dir = 0; dir < 2; dir++) {
                 const uint32_t* o = blk[s * 2 + dir];
-                const v4u32_t out = {o[0] ^ (cw[s].x & tmask), o[1] ^ (cw[s].y & tmask), o[2] ^ (cw[s].z & tmask),
-                                     o[3] ^ (cw[s].w & tmask)};
-                const size_t de = (size_t)(2 * e + dir) * 2 + s;
-                __builtin_nontemporal_store(out, reinterpret_cast<v4u32_t*>(J.dst_seed + de * npad + c));
-                if (lane == 0) {
-                    // new_bit = tau.bits[dir] ^ (t & cw.bits[dir]);
-                    // new_y = tau.y_bits[dir] ^ (t & cw.y_bits[dir]) ^ y   (ibDCF.rs:211-219)
-                    J.dst_t[de * nw + w] = pb[s * 2 + dir] ^ (tw[s] & cwp[s][dir]);
-                    J.dst_y[de * nw + w] = py[s * 2 + dir] ^ (tw[s] & cwp[s][2 + dir]) ^ yw[s];
-                }
+                out[2 * dir + s] = v4u32_t{o[0] ^ (cw[s].x & tmask), o[1] ^ (cw[s].y & tmask), o[2] ^ (cw[s].z & tmask),
+                                           o[3] ^ (cw[s].w & tmask)};
+                // new_bit = tau.bits[dir] ^ (t & cw.bits[dir]);
+                // new_y = tau.y_bits[dir] ^ (t & cw.y_bits[dir]) ^ y   (ibDCF.rs:211-219)
+                tq[2 * dir + s] = pb[s * 2 + dir] ^ (tw[s] & cwp[s][dir]);
+                yq[2 * dir + s] = py[s * 2 + dir] ^ (tw[s] & cwp[s][2 + dir]) ^ yw[s];
             }
         }
+        // The child t / y words go first, then the next entry's parent words are requested, then the 4 child
+        // seeds are stored: behind the request stand exactly 4 stores on every path, so the counted wait at the
+        // loop's top leaves all of them outstanding (a store in a lane-masked region behind the request is
+        // counted along the path that skips it, and the wait then takes the first stores with it).
+        if (lane == 0) {
+#pragma unroll
+            for (int q = 0; q < 4; q++) {
+                J.dst_t[((size_t)4 * e + q) * nw + w] = tq[q];
+                J.dst_y[((size_t)4 * e + q) * nw + w] = yq[q];
+            }
+        }
+        if (kPrefetch && more) fetch(src);
+#pragma unroll
+        for (int q = 0; q < 4; q++)
+            __builtin_nontemporal_store(out[q], reinterpret_cast<v4u32_t*>(J.dst_seed + ((size_t)4 * e + q) * npad + c));
     }
 }
 
