@@ -56,6 +56,7 @@ EXPORTS = [
     "fhh_party_node_sums", "fhh_party_bytes_sent", "fhh_gc_party_test_cfgs", "fhh_memcpy_device",
     "fhh_cot_extend_host", "fhh_cot_extend_ss_host", "fhh_gc_cot_host", "fhh_gt_cot_host", "fhh_gt_cot_ring32_host",
     "fhh_shard_plan", "fhh_reserve_clients", "fhh_add_keys_bincode_append",
+    "fhh_bincode_request_bytes", "fhh_export_keys_bincode",
 ]
 
 
@@ -112,7 +113,7 @@ class FhhSimConfig(ctypes.Structure):
     ]
 
 
-SOURCES = ("fhh_kernels.hip", "fhh_sketch.hip", "fhh_gc.hip", "fhh_ot.hip", "fhh_loop.hip",
+SOURCES = ("fhh_kernels.hip", "fhh_bincode_out.hip", "fhh_sketch.hip", "fhh_gc.hip", "fhh_ot.hip", "fhh_loop.hip",
            "fhh_microbench.hip", "fhh_host.cpp", "fhh_gcot.cpp", "fhh_group.cpp", "fhh_comm.cpp", "fhh_base_ot.cpp")
 
 
@@ -313,6 +314,8 @@ def lib():
         "fhh_add_keys_bincode": (i, [vp, u8p, u64]),
         "fhh_reserve_clients": (i, [vp, u64]),
         "fhh_add_keys_bincode_append": (i, [vp, u8p, u64]),
+        "fhh_bincode_request_bytes": (i, [u32, u32, u64, u64, u64p]),
+        "fhh_export_keys_bincode": (i, [vp, u64, u64, u64, u8p, u64, u64p]),
         "fhh_num_clients": (i, [vp, u64p]),
         "fhh_export_keys": (i, [vp, u8p, u8p, u8p, u8p]),
         "fhh_tree_init": (i, [vp]),

@@ -142,6 +142,22 @@ class KeyCollection:
         self._chk(lib().fhh_export_keys(self._h, ptr(ki), ptr(rs), ptr(cs), ptr(cb)))
         return ki, rs, cs, cb
 
+    def export_keys_bincode(self, first: int = 0, count: int | None = None, batch: int = 0) -> np.ndarray:
+        """Clients [first, first + count) of the device keys as consecutive `add_keys` RPC payloads of
+        `batch` clients each (0: one request; leader.rs:391-415 sends addkey_batch_size = 100), serialized
+        on the GPU: what `add_keys_bincode` / `add_keys_bincode_append` take. One uint8 array holding the
+        requests back to back; `workload.split_add_keys_requests` cuts it. count = None: up to the last
+        client."""
+        if count is None:
+            count = self.num_clients() - first
+        need = ctypes.c_uint64()
+        self._chk(lib().fhh_bincode_request_bytes(self.n_dims, self.depth, count, batch, ctypes.byref(need)))
+        out = np.empty(need.value, np.uint8)
+        got = ctypes.c_uint64()
+        self._chk(lib().fhh_export_keys_bincode(self._h, first, count, batch, ptr(out), out.size, ctypes.byref(got)))
+        assert got.value == out.size
+        return out
+
     def set_client_base(self, base: int):
         self._chk(lib().fhh_set_client_base(self._h, base))
 

@@ -7,6 +7,7 @@
 #pragma once
 #include "fhh_internal.h"
 #include "field_arith.h"
+#include "bincode_emit.h"
 #include "../../include/fhh.h"
 
 #include <hip/hip_runtime.h>
@@ -139,6 +140,7 @@ struct fhh_ctx {
     bool appended = false;
     uint64_t reserved = 0;        // fhh_reserve_clients (0: none)
     DevBuf app_buf, app_err;      // a batch's payload and its error word, kept from call to call
+    DevBuf emit_buf;              // fhh_export_keys_bincode: the serialized requests, kept from call to call
     DimTable tab[kMaxDims];
 
     Phase phase = Phase::kNoInit;
@@ -246,6 +248,14 @@ int append_decode(fhh_ctx* ctx, uint64_t m, const uint8_t* recs, uint32_t* herr)
 void append_commit(fhh_ctx* ctx, uint64_t m);
 int append_rollback(fhh_ctx* ctx);
 std::string bincode_malformed_text(uint32_t herr);
+// fhh_export_keys_bincode on one GPU, as a multi-device ctx drives it per shard: clients [src_first,
+// src_first + m) of ctx's device keys are clients [i0, i0 + m) of an export of `count` clients in requests of B
+// (bincode_emit.h); their bytes [be_slice_begin(i0), be_slice_end(i0, m)) are serialized on ctx's GPU and
+// copied to the same offsets of `out`. Returns when they are there; the ctx is otherwise as before.
+int export_bincode_check(fhh_ctx* ctx, bool have_keys, uint64_t n, uint64_t first, uint64_t count, uint64_t batch,
+                         const uint8_t* out, uint64_t cap, uint64_t* len);   // the refusals; sets *len
+int export_bincode_slice(fhh_ctx* ctx, uint64_t src_first, uint64_t m, uint64_t i0, uint64_t count, uint64_t B,
+                         uint8_t* out);
 bool fmt_is_fe255(uint32_t fmt);
 
 // ---- fhh_group.cpp (multi-device ctx) --------------------------------------------------------
@@ -260,6 +270,8 @@ int group_gen_keys_pair(fhh_ctx* g0, fhh_ctx* g1, uint64_t n, const uint8_t* lef
                         const uint8_t* roots);
 int group_num_clients(const fhh_ctx* g, uint64_t* n);
 int group_export_keys(fhh_ctx* g, uint8_t* key_idx, uint8_t* root_seed, uint8_t* cw_seed, uint8_t* cw_bits);
+int group_export_keys_bincode(fhh_ctx* g, uint64_t first, uint64_t count, uint64_t batch, uint8_t* out, uint64_t cap,
+                              uint64_t* len);
 int group_tree_init(fhh_ctx* g);
 int group_tree_crawl(fhh_ctx* g, bool last, uint64_t* n_children, uint64_t* planes);
 int group_node_sums(fhh_ctx* g, const void* const* vals, bool host, uint64_t ld, uint32_t fmt, void* out_a,

@@ -377,6 +377,24 @@ int group_export_keys(fhh_ctx* g, uint8_t* key_idx, uint8_t* root_seed, uint8_t*
     });
 }
 
+// fhh_export_keys_bincode on a multi-device ctx: [first, first + count) is cut at the shard boundaries and each
+// shard serializes its clients on its own GPU into their byte range of `out` (disjoint ranges: a request that
+// straddles two shards has its u64 m written by the shard of its first client, with the request's own count)
+int group_export_keys_bincode(fhh_ctx* g, uint64_t first, uint64_t count, uint64_t batch, uint8_t* out, uint64_t cap,
+                              uint64_t* len) {
+    Group& G = *g->group;
+    uint64_t n = 0;
+    if (G.placed) group_num_clients(g, &n);
+    int rc = export_bincode_check(g, G.placed && n, n, first, count, batch, out, cap, len);
+    if (rc) return rc;
+    const uint64_t B = be_batch(count, batch), end = first + count;
+    return fan_out(g, [&](size_t k, fhh_ctx* s) {
+        const uint64_t lo = std::max(first, G.base[k]), hi = std::min(end, G.base[k] + G.count[k]);
+        if (lo >= hi) return (int)FHH_OK;
+        return export_bincode_slice(s, lo - G.base[k], hi - lo, lo - first, count, B, out);
+    });
+}
+
 int group_tree_init(fhh_ctx* g) {
     Group& G = *g->group;
     if (g->h_n) {

@@ -793,6 +793,46 @@ static int finish_appended(fhh_ctx* ctx) {
     HIP_TRY(ctx, hipMemcpyAsync(ctx->valid.p, v.data(), ctx->nw * 8, hipMemcpyHostToDevice, ctx->stream));
     return sync(ctx);
 }
+
+// ---- device keys -> add_keys requests (fhh_export_keys_bincode) -------------------------------
+// the refusals both kinds of ctx share; n = the clients on the device(s), have_keys = they are there
+int export_bincode_check(fhh_ctx* ctx, bool have_keys, uint64_t n, uint64_t first, uint64_t count, uint64_t batch,
+                         const uint8_t* out, uint64_t cap, uint64_t* len) {
+    if (!len) return ctx->fail(FHH_E_ARG, "export_keys_bincode: NULL len");
+    if (count == 0) return ctx->fail(FHH_E_ARG, "export_keys_bincode: no clients (an empty request is refused by the decoder too)");
+    const uint64_t R = be_record_bytes(ctx->d, ctx->L), B = be_batch(count, batch);
+    if (count > (~0ull - 8 * be_requests(count, B)) / R) return ctx->fail(FHH_E_ARG, "export_keys_bincode: size overflows");
+    *len = be_total_bytes(count, B, R);
+    if (!have_keys)
+        return ctx->fail(FHH_E_STATE, "export_keys_bincode: no keys on the device (keys staged by fhh_add_keys are "
+                                      "uploaded at fhh_tree_init)");
+    if (first > n || count > n - first)
+        return ctx->fail(FHH_E_ARG, "export_keys_bincode: clients [" + std::to_string(first) + ", " +
+                                        std::to_string(first) + " + " + std::to_string(count) + ") of " + std::to_string(n));
+    if (!out) return ctx->fail(FHH_E_ARG, "export_keys_bincode: NULL out");
+    if (cap < *len)
+        return ctx->fail(FHH_E_ARG, "export_keys_bincode: " + std::to_string(*len) + " bytes needed, cap " + std::to_string(cap));
+    return FHH_OK;
+}
+
+int export_bincode_slice(fhh_ctx* ctx, uint64_t src_first, uint64_t m, uint64_t i0, uint64_t count, uint64_t B,
+                         uint8_t* out) {
+    if (m == 0) return FHH_OK;
+    int rc = set_device(ctx);
+    if (rc) return rc;
+    if (!ctx->dev_keys || src_first + m > ctx->n) return ctx->fail(FHH_E_STATE, "export_keys_bincode: slice outside the device keys");
+    const uint64_t R = be_record_bytes(ctx->d, ctx->L);
+    const uint64_t lo = be_slice_begin(i0, B, R), hi = be_slice_end(i0, m, B, R), org = lo & ~3ull;
+    HIP_TRY(ctx, ctx->emit_buf.ensure(hi - org));
+    uint8_t* stg = ctx->emit_buf.as<uint8_t>();
+    HIP_TRY(ctx, launch_bincode_emit(ctx->cw_seed.as<uint4>(), ctx->cw_bits.as<uint64_t>(), ctx->root_seed.as<uint4>(),
+                                     ctx->key_idx.as<uint64_t>(), ctx->d, ctx->L, (uint32_t)ctx->npad, (uint32_t)ctx->nw,
+                                     src_first, m, i0, count, B, stg, org, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(out + lo, stg + (lo - org), hi - lo, hipMemcpyDeviceToHost, ctx->stream));
+    // the stream alone: timing events and pinned staging of a crawl in progress stay pending
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return FHH_OK;
+}
 }  // namespace eng
 }  // namespace fhh
 
@@ -2143,6 +2183,29 @@ int fhh_export_keys(fhh_ctx* ctx, uint8_t* key_idx, uint8_t* root_seed, uint8_t*
             }
         }
     return FHH_OK;
+}
+
+int fhh_bincode_request_bytes(uint32_t n_dims, uint32_t data_len, uint64_t count, uint64_t batch, uint64_t* bytes) {
+    if (!bytes || count == 0 || n_dims < 1 || n_dims > (uint32_t)kMaxDims || data_len == 0) {
+        g_err = "bincode_request_bytes: count = 0, n_dims outside 1..4, data_len = 0 or NULL bytes";
+        return FHH_E_ARG;
+    }
+    const uint64_t R = be_record_bytes(n_dims, data_len), B = be_batch(count, batch);
+    if (count > (~0ull - 8 * be_requests(count, B)) / R) {
+        g_err = "bincode_request_bytes: size overflows";
+        return FHH_E_ARG;
+    }
+    *bytes = be_total_bytes(count, B, R);
+    return FHH_OK;
+}
+
+int fhh_export_keys_bincode(fhh_ctx* ctx, uint64_t first, uint64_t count, uint64_t batch, uint8_t* out, uint64_t cap,
+                            uint64_t* len) {
+    CTX_CHECK(ctx);
+    if (ctx->group) return group_export_keys_bincode(ctx, first, count, batch, out, cap, len);
+    const int rc = export_bincode_check(ctx, ctx->dev_keys && ctx->n, ctx->n, first, count, batch, out, cap, len);
+    if (rc) return rc;
+    return export_bincode_slice(ctx, first, count, 0, count, be_batch(count, batch), out);
 }
 
 int fhh_add_keys_bincode(fhh_ctx* ctx, const uint8_t* req, uint64_t len) {

@@ -339,6 +339,13 @@ hipError_t launch_repitch_seeds(const uint4* src, uint4* dst, uint64_t rows, uin
                                 uint64_t dst_pitch, hipStream_t stream);
 hipError_t launch_repitch_words(const uint64_t* src, uint64_t* dst, uint64_t rows, uint64_t width, uint64_t src_pitch,
                                 uint64_t dst_pitch, hipStream_t stream);
+// fhh_bincode_out.hip: clients [src_first, src_first + m) of the layout as clients [i0, i0 + m) of an export of
+// `count` clients in requests of B (bincode_emit.h); byte g of the export goes to stg[g - org], org % 4 == 0 and
+// org <= be_slice_begin(i0), stg holding be_slice_end(i0, m) - org bytes
+hipError_t launch_bincode_emit(const uint4* cw_seed, const uint64_t* cw_bits, const uint4* root_seed,
+                               const uint64_t* key_idx, uint32_t d, uint32_t L, uint32_t npad, uint32_t nw,
+                               uint64_t src_first, uint64_t m, uint64_t i0, uint64_t count, uint64_t B, uint8_t* stg,
+                               uint64_t org, hipStream_t stream);
 // occupancy-derived persistent grid for k_expand variant on `device`
 int expand_grid(int device, int variant);
 // RCCL all-reduce (sum, u64) on `stream` (fhh_comm.cpp); asynchronous

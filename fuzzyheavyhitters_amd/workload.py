@@ -289,3 +289,22 @@ def add_keys_request_bincode(key_idx: np.ndarray, root_seed: np.ndarray, cw_seed
     for b in range(4):
         cw[:, :, :, 16 + b] = (nib >> b) & 1
     return np.concatenate([np.frombuffer(np.uint64(n).tobytes(), np.uint8), rec.reshape(-1)])
+
+
+def split_add_keys_requests(buf: np.ndarray, n_dims: int, data_len: int) -> list:
+    """Cut concatenated `add_keys` requests (`KeyCollection.export_keys_bincode` with a batch size) into
+    the single requests, as views of `buf`: each is its u64 client count m and m records of
+    8 + 2 d (25 + 20 L) bytes. The leader's send loop (leader.rs:391-415) is one RPC per element."""
+    buf = np.ascontiguousarray(buf, np.uint8).reshape(-1)
+    R = 8 + 2 * n_dims * (25 + 20 * data_len)
+    out, a = [], 0
+    while a < buf.size:
+        if buf.size - a < 8:
+            raise ValueError(f"split_add_keys_requests: {buf.size - a} stray bytes at offset {a}")
+        m = int(buf[a:a + 8].view("<u8")[0])
+        b = a + 8 + m * R
+        if m == 0 or b > buf.size:
+            raise ValueError(f"split_add_keys_requests: request of {m} clients at offset {a} does not fit")
+        out.append(buf[a:b])
+        a = b
+    return out

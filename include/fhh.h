@@ -157,6 +157,33 @@ int fhh_num_clients(const fhh_ctx* ctx, uint64_t* n);
 /* Copy this ctx's keys back in add_keys layout (for parity checks). Any pointer may be NULL. */
 int fhh_export_keys(fhh_ctx* ctx, uint8_t* key_idx, uint8_t* root_seed, uint8_t* cw_seed, uint8_t* cw_bits);
 
+/* The leader's half of the `add_keys` RPC (leader.rs:391-415): device keys out as the requests a server takes
+ * with fhh_add_keys_bincode / fhh_add_keys_bincode_append, the inverse of those two.
+ *
+ * fhh_bincode_request_bytes is host arithmetic, no GPU: the bytes of the requests that serialize `count`
+ * clients in batches of `batch` (batch = 0: one request): 8 * ceil(count / B) + count * R, B = batch ? batch :
+ * count, R = 8 + 2 d (25 + 20 L). FHH_E_ARG for count = 0, n_dims outside 1..4, data_len = 0.
+ *
+ * fhh_export_keys_bincode writes clients [first, first + count) of this ctx's device keys as consecutive
+ * AddKeysRequest.keys payloads (rpc.rs:12-15, bincode 1.x legacy: u64 m, then m client records = u64 d,
+ * d x (left, right) ibDCFKey), request q holding clients first + q B .. min(first + (q + 1) B, first + count)
+ * - 1, back to back in `out` (host memory, cap bytes); *len = fhh_bincode_request_bytes(...). The bytes are
+ * serialized on the GPU from the device layout, into a device staging buffer of *len bytes that the ctx keeps
+ * and reuses: the range is the caller's lever on memory (at L = 512 a client is 20.5 KB per server, so a 1M
+ * population is exported in ranges). It works on any ctx whose keys are on the device: after
+ * fhh_gen_keys_pair, fhh_add_keys_bincode, appended batches (before and after fhh_tree_init), or
+ * fhh_add_keys once fhh_tree_init has uploaded them. FHH_E_STATE if the ctx holds no keys or only keys staged
+ * by fhh_add_keys. FHH_E_ARG, with nothing written to `out` and *len set where it can be, for count = 0 (the
+ * decoder refuses an empty request too), first + count > n, a NULL out or len, cap below the needed bytes.
+ * The ctx is not changed (phase, frontier, pending children, stats, party state): the call may come between
+ * the levels of a crawl; it runs on the ctx's stream and returns when `out` is complete. On a multi-device
+ * ctx the range is cut at the shard boundaries (fhh_shard_info) and each shard serializes its clients on its
+ * own GPU into their byte range of `out`; a request that straddles two shards carries its own count, written
+ * by the shard of its first client; the bytes are those of a one-GPU ctx holding the same clients. */
+int fhh_bincode_request_bytes(uint32_t n_dims, uint32_t data_len, uint64_t count, uint64_t batch, uint64_t* bytes);
+int fhh_export_keys_bincode(fhh_ctx* ctx, uint64_t first, uint64_t count, uint64_t batch, uint8_t* out, uint64_t cap,
+                            uint64_t* len);
+
 /* ---- crawl ---------------------------------------------------------------------------- */
 
 /* tree_init (collect.rs:67-92) with eval_init per key (ibDCF.rs:229-236). */
