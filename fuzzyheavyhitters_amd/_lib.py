@@ -114,7 +114,8 @@ class FhhSimConfig(ctypes.Structure):
 
 
 SOURCES = ("fhh_kernels.hip", "fhh_bincode_out.hip", "fhh_sketch.hip", "fhh_gc.hip", "fhh_ot.hip", "fhh_loop.hip",
-           "fhh_microbench.hip", "fhh_host.cpp", "fhh_gcot.cpp", "fhh_group.cpp", "fhh_comm.cpp", "fhh_base_ot.cpp")
+           "fhh_microbench.hip", "fhh_host.cpp", "fhh_keys_io.cpp", "fhh_sim_crawl.cpp", "fhh_sketch_host.cpp",
+           "fhh_gcot.cpp", "fhh_gcot_harness.cpp", "fhh_group.cpp", "fhh_comm.cpp", "fhh_base_ot.cpp")
 
 
 class FhhSketchBatch(ctypes.Structure):

@@ -1,9 +1,13 @@
 // Engine state shared by the host sources — not part of the public C ABI (include/fhh.h):
-//   fhh_host.cpp   one server's KeyCollection on one GPU (engine, device level loop, C ABI)
-//   fhh_group.cpp  one KeyCollection over several GPUs: clients sharded in 64-client words,
-//                  per-child partials reduced over an in-process RCCL communicator
-//   fhh_gcot.cpp   the GC equality test + OT extension of tree_crawl and their two-party split
-//                  (each server's half on its own ctx; only byte buffers cross)
+//   fhh_host.cpp         one server's KeyCollection on one GPU (the engine core and its C ABI)
+//   fhh_keys_io.cpp      add_keys requests in bincode: decode, append and export
+//   fhh_sim_crawl.cpp    the in-process two-server harness: fhh_sim_*, the device-resident level loop
+//   fhh_sketch_host.cpp  sketch + Beaver verification wrappers
+//   fhh_group.cpp        one KeyCollection over several GPUs: clients sharded in 64-client words,
+//                        per-child partials reduced over an in-process RCCL communicator
+//   fhh_gcot.cpp         the GC equality test + OT extension of tree_crawl and their two-party split
+//                        (each server's half on its own ctx; only byte buffers cross)
+//   fhh_gcot_harness.cpp their one-shot test entry points on host buffers
 #pragma once
 #include "fhh_internal.h"
 #include "field_arith.h"
@@ -104,7 +108,7 @@ enum class Phase { kNoInit, kFrontier, kPending, kPendingLast };
 using Limbs10 = std::array<uint32_t, 10>;
 
 struct Group;       // fhh_group.cpp: shards of a multi-device ctx
-struct PartyState;  // fhh_party.cpp: one server's half of a level's GC + OT
+struct PartyState;  // fhh_gcot.cpp: one server's half of a level's GC + OT
 
 }  // namespace eng
 }  // namespace fhh
@@ -223,6 +227,54 @@ int ctx_sync(fhh_ctx* ctx);         // drain the ctx stream, retire its timing e
 int ctx_set_device(fhh_ctx* ctx);   // hipSetDevice(ctx->device)
 ChildArgs ctx_child_args(fhh_ctx* ctx);   // the pending crawl's children as k_share_planes reads them
 
+// what fhh_sim_crawl.cpp and fhh_keys_io.cpp take from the engine core, and fhh_tree_init from fhh_keys_io.cpp:
+// between the library's own sources only, so not among its dynamic symbols
+#pragma GCC visibility push(hidden)
+// an event pair around what follows on the ctx stream; ctx_sync adds its time to the stats `blocks` selects
+hipError_t timing_begin(fhh_ctx* ctx, size_t* slot);
+hipError_t timing_end(fhh_ctx* ctx, size_t slot, uint64_t blocks);
+// `blocks` tags of the event pairs that bracket the level loop's cross-rank all-reduce and its
+// GC + OT step (share planes to the last chunk's sums)
+constexpr uint64_t kAllreduceTag = ~0ull;
+constexpr uint64_t kGcotTag = ~1ull;
+// Pair mode (in-process two-server harness): c1 runs on c0's stream, so one stream carries
+// both servers' work in order and the level loop needs a single host sync.
+struct PairScope {
+    fhh_ctx *c0, *c1;
+    PairScope(fhh_ctx* a, fhh_ctx* b) : c0(a), c1(b) {
+        c1->stream = c0->stream;
+        c0->peer = c1;
+    }
+    ~PairScope() {
+        (void)hipStreamSynchronize(c0->stream);
+        c1->stream = c1->own_stream;
+        c0->peer = nullptr;
+    }
+};
+int crawl_pair(fhh_ctx* c0, fhh_ctx* c1, bool last);
+ChildArgs child_args(fhh_ctx* c0, fhh_ctx* c1);   // ctx_child_args with server 1's tables from c1 (NULL: c0's)
+int prune_impl(fhh_ctx* ctx, const uint8_t* keep, uint64_t n);
+// FE255 values as arrays over field_arith.h's pointer forms: 8 u64 limb sums (limb k weight 2^(32k)) carry-propagated
+// into 10 u32 limbs; their reduction mod p; a - b mod p
+inline Limbs10 limbs_from_partials(const uint64_t* p8) {
+    Limbs10 out{};
+    fhh::limbs10_from_partials(p8, out.data());
+    return out;
+}
+inline std::array<uint32_t, 8> fe255_reduce(const Limbs10& x) {
+    std::array<uint32_t, 8> out{};
+    fhh::fe255_reduce(x.data(), out.data());
+    return out;
+}
+inline std::array<uint32_t, 8> fe255_sub(const std::array<uint32_t, 8>& a, const std::array<uint32_t, 8>& b) {
+    std::array<uint32_t, 8> out{};
+    fhh::fe255_sub(a.data(), b.data(), out.data());
+    return out;
+}
+int alloc_keys(fhh_ctx* ctx, uint64_t n);   // the key buffers and `valid` of n clients (a one-shot layout)
+int finish_appended(fhh_ctx* ctx);          // fhh_keys_io.cpp: tree_init on appended keys
+#pragma GCC visibility pop
+
 // tree_crawl(_last)'s expansion; the share planes [C][2d][nw] (NULL: none) go to a host buffer
 // whose rows are pitch_words u64 wide, this ctx's words starting at word_off (a shard of a
 // multi-device ctx writes its 64-client words into the group's planes in place)
@@ -236,6 +288,9 @@ int node_partials(fhh_ctx* ctx, const void* vals, uint32_t fmt, uint64_t ld, uin
 // canonical FE sums [C] / unreduced [C][10] + canonical [C][8] FE255 sums from reduced partials;
 // FE255 sums of a pending crawl_last become the frontier_last values (collect.rs:909-914)
 int node_sums_finish(fhh_ctx* ctx, const uint64_t* partials, uint32_t fmt, void* out_a, void* out_b);
+bool fmt_is_fe255(uint32_t fmt);
+
+// ---- fhh_keys_io.cpp -------------------------------------------------------------------------
 // the add_keys RPC payload's n client records (without the leading u64), decoded on the device
 int add_keys_bincode_records(fhh_ctx* ctx, uint64_t n, const uint8_t* recs);
 // fhh_reserve_clients / fhh_add_keys_bincode_append on a one-GPU ctx, in the steps a multi-device ctx drives
@@ -256,7 +311,6 @@ int export_bincode_check(fhh_ctx* ctx, bool have_keys, uint64_t n, uint64_t firs
                          const uint8_t* out, uint64_t cap, uint64_t* len);   // the refusals; sets *len
 int export_bincode_slice(fhh_ctx* ctx, uint64_t src_first, uint64_t m, uint64_t i0, uint64_t count, uint64_t B,
                          uint8_t* out);
-bool fmt_is_fe255(uint32_t fmt);
 
 // ---- fhh_group.cpp (multi-device ctx) --------------------------------------------------------
 void group_destroy(fhh_ctx* g);
@@ -311,6 +365,8 @@ int ot_host_keys(fhh_ctx* ctx, const uint8_t seeds[128 * 2 * 16], const uint8_t 
 // m OTs of OtArgs a's mode on ctx's stream (fhh_gcot.cpp): sizes, scratch matrices and messages are
 // set here; tr (optional) receives the transcript's device pointers
 int ot_run(fhh_ctx* ctx, OtArgs a, uint64_t m, OtOut* tr);
+// the transcript's U in row form [u_rows][ceil(m / 128)][16], to the host
+int u_transcript(fhh_ctx* ctx, const OtOut& tr, uint64_t m, uint8_t* u_out);
 // row-PRG blocks a batch of m OTs takes from its base-OT session (a multiple of 256)
 uint64_t ot_session_blocks(uint64_t m);
 

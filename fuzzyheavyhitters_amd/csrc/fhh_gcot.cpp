@@ -1,8 +1,9 @@
 // Host side of row f1: the garbled-circuit equality test and the OT extension of tree_crawl
 // (src/equalitytest.rs:25-219, src/collect.rs:419-482) — key schedules and per-level material,
-// the OT-extension runner the device level loop and the C ABI share, the one-process C ABI
-// (fhh_gc_equality_*, fhh_ot_extend_*), and the two-party split (fhh_gb_* / fhh_ev_*: each server
-// runs its half on its own ctx, only the protocol messages cross).
+// the OT-extension runner the device level loop and the C ABI share, the one-process C ABI on device
+// buffers (fhh_gc_equality_device, fhh_ot_extend_device), and the two-party split (fhh_gb_* / fhh_ev_*:
+// each server runs its half on its own ctx, only the protocol messages cross). The one-shot test entry
+// points on host buffers are in fhh_gcot_harness.cpp.
 #include "fhh_engine.h"
 #include "aes_tables.h"
 #include "field_arith.h"
@@ -246,74 +247,6 @@ int fhh_gc_equality_device(fhh_ctx* ctx, const fhh_gc_batch* b) {
     return ctx_sync(ctx);
 }
 
-int fhh_gc_equality_host(fhh_ctx* ctx, uint64_t n, uint32_t bits, const uint8_t* gb_bits, const uint8_t* ev_bits,
-                         uint32_t mask, const uint8_t label_key[16], const uint8_t delta[16], uint64_t label_nonce,
-                         uint64_t gate_base, uint8_t* tables, uint8_t* gb_labels, uint8_t* ev_labels,
-                         uint8_t* decode, uint8_t* out) {
-    CTX_CHECK(ctx);
-    int rc = ctx_set_device(ctx);
-    if (rc) return rc;
-    if (bits < 1 || bits > (uint32_t)kGcMaxBits) return ctx->fail(FHH_E_ARG, "gc: bits must be in [1, 8]");
-    if (n == 0) return FHH_OK;
-    if (!gb_bits || !ev_bits || !label_key || !delta || !out) return ctx->fail(FHH_E_ARG, "gc: NULL argument");
-    if (n > 0xFFFFFFFFull) return ctx->fail(FHH_E_ARG, "gc: n must fit 32 bits");
-    const uint64_t nw = (n + 63) / 64;
-    std::vector<uint64_t> planes[2];
-    const uint8_t* src[2] = {gb_bits, ev_bits};
-    for (int s = 0; s < 2; s++) {
-        planes[s].assign((size_t)bits * nw, 0);
-        for (uint64_t t = 0; t < n; t++)
-            for (uint32_t j = 0; j < bits; j++)
-                if (src[s][t * bits + j] & 1) planes[s][(size_t)j * nw + t / 64] |= 1ull << (t % 64);
-    }
-    DevBuf dp[2], dt, dg, de, dd, dout;
-    for (int s = 0; s < 2; s++) {
-        HIP_TRY(ctx, dp[s].ensure(planes[s].size() * 8));
-        HIP_TRY(ctx, hipMemcpyAsync(dp[s].p, planes[s].data(), planes[s].size() * 8, hipMemcpyHostToDevice, ctx->stream));
-    }
-    HIP_TRY(ctx, dt.ensure((size_t)std::max(bits - 1, 1u) * 2 * n * 16));
-    HIP_TRY(ctx, dg.ensure((size_t)(bits + 1) * n * 16));
-    HIP_TRY(ctx, de.ensure((size_t)bits * n * 16));
-    HIP_TRY(ctx, dd.ensure(n));
-    HIP_TRY(ctx, dout.ensure(n));
-    fhh_gc_batch b{};
-    b.groups = 1;
-    b.clients = (uint32_t)n;
-    b.words = (uint32_t)nw;
-    b.bits = bits;
-    b.mask = mask;
-    std::memcpy(b.label_key, label_key, 16);
-    std::memcpy(b.delta, delta, 16);
-    b.label_nonce = label_nonce;
-    b.gate_base = gate_base;
-    b.gb_planes_dev = dp[0].as<uint64_t>();
-    b.ev_planes_dev = dp[1].as<uint64_t>();
-    b.tables_dev = dt.as<uint8_t>();
-    b.gb_labels_dev = dg.as<uint8_t>();
-    b.ev_labels_dev = de.as<uint8_t>();
-    b.decode_dev = dd.as<uint8_t>();
-    b.out_dev = dout.as<uint8_t>();
-    rc = fhh_gc_equality_device(ctx, &b);
-    if (rc) return rc;
-    HIP_TRY(ctx, hipMemcpy(out, dout.p, n, hipMemcpyDeviceToHost));
-    if (decode) HIP_TRY(ctx, hipMemcpy(decode, dd.p, n, hipMemcpyDeviceToHost));
-    // SoA [row][t][16] -> AoS [t][row][16]
-    auto soa_to_aos = [&](const DevBuf& d, uint32_t rows, uint8_t* dst) -> int {
-        if (!dst || rows == 0) return FHH_OK;
-        std::vector<uint8_t> h((size_t)rows * n * 16);
-        HIP_TRY(ctx, hipMemcpy(h.data(), d.p, h.size(), hipMemcpyDeviceToHost));
-        for (uint32_t r = 0; r < rows; r++)
-            for (uint64_t t = 0; t < n; t++)
-                std::memcpy(dst + (t * rows + r) * 16, h.data() + ((size_t)r * n + t) * 16, 16);
-        return FHH_OK;
-    };
-    rc = soa_to_aos(dt, 2 * (bits - 1), tables);
-    if (rc) return rc;
-    rc = soa_to_aos(dg, bits + 1, gb_labels);
-    if (rc) return rc;
-    return soa_to_aos(de, bits, ev_labels);
-}
-
 // ---- OT extension (row f1's OT) ---------------------------------------------------------------
 int fhh_ot_extend_device(fhh_ctx* ctx, const fhh_ot_batch* b) {
     CTX_CHECK(ctx);
@@ -346,363 +279,6 @@ int fhh_ot_extend_device(fhh_ctx* ctx, const fhh_ot_batch* b) {
     return ctx_sync(ctx);
 }
 
-int fhh_ot_extend_host(fhh_ctx* ctx, uint64_t m, const uint8_t* choices, const uint8_t* x0, const uint8_t* x1,
-                       const uint8_t delta[16], const uint8_t base_seeds[128 * 2 * 16], const uint8_t base_choice[16],
-                       uint64_t tweak_base, uint8_t* out, uint8_t* u_out, uint8_t* y0_out, uint8_t* y1_out) {
-    CTX_CHECK(ctx);
-    int rc = ctx_set_device(ctx);
-    if (rc) return rc;
-    if (m == 0) return FHH_OK;
-    if (!choices || !x0 || !out || !base_seeds || !base_choice || (!x1 && !delta))
-        return ctx->fail(FHH_E_ARG, "ot_extend: NULL argument");
-    const uint64_t mp = ot_padded(m);
-    std::vector<uint32_t> bits(mp / 32, 0);
-    for (uint64_t j = 0; j < m; j++)
-        if (choices[j] & 1) bits[j / 32] |= 1u << (j % 32);
-    uint32_t* ch = nullptr;
-    HIP_TRY(ctx, ot_choices_buffer(ctx, m, &ch));
-    HIP_TRY(ctx, hipMemcpyAsync(ch, bits.data(), mp / 8, hipMemcpyHostToDevice, ctx->stream));
-    DevBuf d0, d1, dout;
-    HIP_TRY(ctx, d0.ensure(m * 16));
-    HIP_TRY(ctx, dout.ensure(m * 16));
-    HIP_TRY(ctx, hipMemcpyAsync(d0.p, x0, m * 16, hipMemcpyHostToDevice, ctx->stream));
-    if (x1) {
-        HIP_TRY(ctx, d1.ensure(m * 16));
-        HIP_TRY(ctx, hipMemcpyAsync(d1.p, x1, m * 16, hipMemcpyHostToDevice, ctx->stream));
-    }
-    OtOut tr;
-    const uint32_t* rk = nullptr;
-    rc = ot_host_keys(ctx, base_seeds, base_choice, &rk);
-    if (rc) return rc;
-    OtArgs a{};
-    a.rk = rk;
-    words_from_bytes(base_choice, a.s);
-    a.choices = ch;
-    a.x0 = d0.as<uint4>();
-    a.x1 = x1 ? d1.as<uint4>() : nullptr;
-    if (!x1) words_from_bytes(delta, a.delta);
-    a.out = dout.as<uint4>();
-    a.tweak_base = tweak_base;
-    rc = ot_run(ctx, a, m, &tr);
-    if (rc) return rc;
-    rc = ctx_sync(ctx);
-    if (rc) return rc;
-    HIP_TRY(ctx, hipMemcpy(out, dout.p, m * 16, hipMemcpyDeviceToHost));
-    if (y0_out) HIP_TRY(ctx, hipMemcpy(y0_out, tr.Y0, m * 16, hipMemcpyDeviceToHost));
-    if (y1_out) HIP_TRY(ctx, hipMemcpy(y1_out, tr.Y1, m * 16, hipMemcpyDeviceToHost));
-    if (u_out) {   // rows [128][ceil(m / 128)] of the padded tile-major matrix
-        rc = u_transcript(ctx, tr, m, u_out);
-        if (rc) return rc;
-    }
-    return FHH_OK;
-}
-
-int fhh_cot_extend_ss_host(fhh_ctx* ctx, uint32_t ss_k, uint64_t m, uint32_t mode, const uint8_t* choices,
-                           const uint8_t delta[16], uint32_t mask, const uint8_t base_seeds[128 * 2 * 16],
-                           const uint8_t base_choice[16], uint64_t ctr_off, uint8_t* sender_out, uint8_t* out,
-                           uint8_t* u_out, uint8_t* y_out, uint8_t* corr_out) {
-    CTX_CHECK(ctx);
-    int rc = ctx_set_device(ctx);
-    if (rc) return rc;
-    if (ss_k != 1 && ss_k != 2 && ss_k != 4) return ctx->fail(FHH_E_ARG, "cot_extend: ss_k must be 1, 2 or 4");
-    if (mode < FHH_COT_LABELS || mode > FHH_COT_RAW) return ctx->fail(FHH_E_ARG, "cot_extend: mode must be 1..4");
-    if (m == 0) return FHH_OK;
-    if (!choices || !out || !base_seeds || !base_choice || (mode == FHH_COT_LABELS && !delta))
-        return ctx->fail(FHH_E_ARG, "cot_extend: NULL argument");
-    if (mode == FHH_COT_FE255 && (m % 2)) return ctx->fail(FHH_E_ARG, "cot_extend: FieldElm shares take OT pairs (m even)");
-    const uint64_t mp = ot_padded(m);
-    std::vector<uint32_t> bits(mp / 32, 0);
-    for (uint64_t j = 0; j < m; j++)
-        if (choices[j] & 1) bits[j / 32] |= 1u << (j % 32);
-    if (mode == FHH_COT_FE255)
-        for (uint64_t t = 0; 2 * t < m; t++)
-            if (((bits[(2 * t) / 32] >> ((2 * t) % 32)) & 1u) != ((bits[(2 * t + 1) / 32] >> ((2 * t + 1) % 32)) & 1u))
-                return ctx->fail(FHH_E_ARG, "cot_extend: a FieldElm OT pair needs one choice for both halves");
-    uint32_t* ch = nullptr;
-    HIP_TRY(ctx, ot_choices_buffer(ctx, m, &ch));
-    HIP_TRY(ctx, hipMemcpyAsync(ch, bits.data(), mp / 8, hipMemcpyHostToDevice, ctx->stream));
-    const size_t per = mode == FHH_COT_FE ? 8 : 16;   // bytes per OT of out / sender values / y
-    DevBuf dsx, dout;
-    HIP_TRY(ctx, dsx.ensure(m * per));
-    HIP_TRY(ctx, dout.ensure(m * per));
-    const uint32_t* rk = nullptr;
-    rc = ot_host_keys(ctx, base_seeds, base_choice, &rk);
-    if (rc) return rc;
-    OtArgs a{};
-    a.mode = mode;
-    a.mask = mask & 1u;
-    a.rk = rk;
-    words_from_bytes(base_choice, a.s);
-    a.choices = ch;
-    if (delta) words_from_bytes(delta, a.delta);
-    a.ctr_off = ctr_off;
-    a.sx = dsx.p;
-    a.out = dout.as<uint4>();
-    a.ss_k = ss_k;
-    OtOut tr;
-    rc = ot_run(ctx, a, m, &tr);
-    if (rc) return rc;
-    rc = ctx_sync(ctx);
-    if (rc) return rc;
-    HIP_TRY(ctx, hipMemcpy(out, dout.p, m * per, hipMemcpyDeviceToHost));
-    if (sender_out) HIP_TRY(ctx, hipMemcpy(sender_out, dsx.p, m * per, hipMemcpyDeviceToHost));
-    if (y_out && mode != FHH_COT_RAW) HIP_TRY(ctx, hipMemcpy(y_out, tr.Y0, m * per, hipMemcpyDeviceToHost));
-    if (u_out) {
-        rc = u_transcript(ctx, tr, m, u_out);
-        if (rc) return rc;
-    }
-    if (corr_out && ss_k > 1) HIP_TRY(ctx, hipMemcpy(corr_out, tr.corr, (size_t)128 * 2 * 16, hipMemcpyDeviceToHost));
-    return FHH_OK;
-}
-
-int fhh_cot_extend_host(fhh_ctx* ctx, uint64_t m, uint32_t mode, const uint8_t* choices, const uint8_t delta[16],
-                        uint32_t mask, const uint8_t base_seeds[128 * 2 * 16], const uint8_t base_choice[16],
-                        uint64_t ctr_off, uint8_t* sender_out, uint8_t* out, uint8_t* u_out, uint8_t* y_out) {
-    return fhh_cot_extend_ss_host(ctx, 1, m, mode, choices, delta, mask, base_seeds, base_choice, ctr_off, sender_out,
-                                  out, u_out, y_out, nullptr);
-}
-
-int fhh_gc_cot_host(fhh_ctx* ctx, uint64_t n, uint32_t bits, const uint8_t* gb_bits, const uint8_t* ev_bits,
-                    uint32_t mask, uint64_t gate_base, const uint8_t base_seeds[128 * 2 * 16],
-                    const uint8_t base_choice[16], uint64_t ctr_off, uint8_t* tables, uint8_t* ev_zero,
-                    uint8_t* ev_active, uint8_t* decode, uint8_t* out, uint64_t* gb_share, uint64_t* ev_share,
-                    uint64_t* share_y) {
-    CTX_CHECK(ctx);
-    int rc = ctx_set_device(ctx);
-    if (rc) return rc;
-    if (bits < 1 || bits > (uint32_t)kGcMaxBits) return ctx->fail(FHH_E_ARG, "gc_cot: bits must be in [1, 8]");
-    if (n == 0) return FHH_OK;
-    if (!gb_bits || !ev_bits || !base_seeds || !base_choice || !out) return ctx->fail(FHH_E_ARG, "gc_cot: NULL argument");
-    if (!(base_choice[0] & 1)) return ctx->fail(FHH_E_ARG, "gc_cot: s is the free-XOR Delta: its bit 0 must be 1");
-    if (n > 0xFFFFFFFFull) return ctx->fail(FHH_E_ARG, "gc_cot: n must fit 32 bits");
-    const bool share = gb_share || ev_share || share_y;
-    if (share && !(gb_share && ev_share && share_y))
-        return ctx->fail(FHH_E_ARG, "gc_cot: gb_share, ev_share and share_y go together");
-    const uint64_t nw = (n + 63) / 64, npad = 64 * nw, m = (uint64_t)bits * npad;
-    std::vector<uint64_t> planes[2];
-    const uint8_t* src[2] = {gb_bits, ev_bits};
-    for (int s = 0; s < 2; s++) {
-        planes[s].assign((size_t)bits * nw + ot_padded(m) / 64, 0);   // the evaluator's: OT choice words, padded
-        for (uint64_t t = 0; t < n; t++)
-            for (uint32_t j = 0; j < bits; j++)
-                if (src[s][t * bits + j] & 1) planes[s][(size_t)j * nw + t / 64] |= 1ull << (t % 64);
-    }
-    DevBuf dp[2], dt, dg, de, da, dd, dout, dsh;
-    for (int s = 0; s < 2; s++) {
-        HIP_TRY(ctx, dp[s].ensure(planes[s].size() * 8));
-        HIP_TRY(ctx, hipMemcpyAsync(dp[s].p, planes[s].data(), planes[s].size() * 8, hipMemcpyHostToDevice, ctx->stream));
-    }
-    HIP_TRY(ctx, dt.ensure((size_t)std::max(bits - 1, 1u) * 2 * n * 16));
-    HIP_TRY(ctx, dg.ensure(16));   // no garbler labels in this protocol (gc_args wants a pointer)
-    HIP_TRY(ctx, de.ensure(m * 16));
-    HIP_TRY(ctx, da.ensure(m * 16));
-    HIP_TRY(ctx, dd.ensure(n));
-    HIP_TRY(ctx, dout.ensure(n));
-    if (share) HIP_TRY(ctx, dsh.ensure(3 * n * 8));   // [gb | y | ev]
-    // 1. the labels OT (OtArgs mode 4): choice bits = the evaluator's planes at OT index j npad + i;
-    // the garbler's zero labels q_j, the evaluator's active labels t_j = q_j ^ r_j s
-    const uint32_t* rk = nullptr;
-    rc = ot_host_keys(ctx, base_seeds, base_choice, &rk);
-    if (rc) return rc;
-    fhh_gc_batch gb{};
-    gb.groups = 1;
-    gb.clients = (uint32_t)n;
-    gb.words = (uint32_t)nw;
-    gb.bits = bits;
-    gb.mask = mask;
-    std::memcpy(gb.delta, base_choice, 16);   // Delta = s; no label key: the garbler draws no labels
-    gb.gate_base = gate_base;
-    gb.gb_planes_dev = dp[0].as<uint64_t>();
-    gb.ev_planes_dev = dp[1].as<uint64_t>();
-    gb.tables_dev = dt.as<uint8_t>();
-    gb.gb_labels_dev = dg.as<uint8_t>();
-    gb.ev_labels_dev = de.as<uint8_t>();
-    gb.decode_dev = dd.as<uint8_t>();
-    gb.out_dev = dout.as<uint8_t>();
-    GcArgs g;
-    rc = gc_args(ctx, &gb, g);
-    if (rc) return rc;
-    OtArgs a{};
-    a.mode = 4;
-    a.rk = rk;
-    words_from_bytes(base_choice, a.s);
-    a.choices = dp[1].as<uint32_t>();
-    a.ctr_off = ctr_off;
-    a.sx = de.p;
-    a.out = da.as<uint4>();
-    rc = ot_run(ctx, a, m, nullptr);
-    if (rc) return rc;
-    // 2. garble on the C-OT's zero labels with the garbler's string and mask folded in, 3. evaluate on the
-    // OT'd active labels
-    g.ev_ot = 1;
-    if (share) {
-        g.sh_gb = dsh.as<uint64_t>();
-        g.sh_y = g.sh_gb + n;
-    }
-    HIP_TRY(ctx, launch_gc_garble(g, ctx->stream));
-    g.ev_labels = da.as<uint4>();
-    g.sh_gb = nullptr;
-    if (share) g.sh_ev = dsh.as<uint64_t>() + 2 * n;
-    HIP_TRY(ctx, launch_gc_eval(g, ctx->stream));
-    rc = ctx_sync(ctx);
-    if (rc) return rc;
-    HIP_TRY(ctx, hipMemcpy(out, dout.p, n, hipMemcpyDeviceToHost));
-    if (share) {
-        HIP_TRY(ctx, hipMemcpy(gb_share, dsh.p, n * 8, hipMemcpyDeviceToHost));
-        HIP_TRY(ctx, hipMemcpy(share_y, dsh.as<uint64_t>() + n, n * 8, hipMemcpyDeviceToHost));
-        HIP_TRY(ctx, hipMemcpy(ev_share, dsh.as<uint64_t>() + 2 * n, n * 8, hipMemcpyDeviceToHost));
-    }
-    if (decode) HIP_TRY(ctx, hipMemcpy(decode, dd.p, n, hipMemcpyDeviceToHost));
-    auto soa_to_aos = [&](const DevBuf& d, uint32_t rows_, uint64_t stride, uint8_t* dst) -> int {
-        if (!dst || rows_ == 0) return FHH_OK;
-        std::vector<uint8_t> h((size_t)rows_ * stride * 16);
-        HIP_TRY(ctx, hipMemcpy(h.data(), d.p, h.size(), hipMemcpyDeviceToHost));
-        for (uint32_t r = 0; r < rows_; r++)
-            for (uint64_t t = 0; t < n; t++)
-                std::memcpy(dst + (t * rows_ + r) * 16, h.data() + ((size_t)r * stride + t) * 16, 16);
-        return FHH_OK;
-    };
-    rc = soa_to_aos(dt, 2 * (bits - 1), n, tables);
-    if (!rc) rc = soa_to_aos(de, bits, npad, ev_zero);
-    if (!rc) rc = soa_to_aos(da, bits, npad, ev_active);
-    return rc;
-}
-
-static int gt_cot_host(fhh_ctx* ctx, uint64_t n, uint32_t bits, const uint8_t* gb_bits, const uint8_t* ev_bits,
-                       uint32_t mask, uint64_t gate_base, const uint8_t base_seeds[128 * 2 * 16],
-                       const uint8_t base_choice[16], uint64_t ctr_off, uint8_t* ev_zero, uint8_t* ev_active,
-                       uint64_t* msgs, uint64_t* gb_share, uint64_t* ev_share, bool ring32) {
-    CTX_CHECK(ctx);
-    int rc = ctx_set_device(ctx);
-    if (rc) return rc;
-    if (bits < 1 || bits > (uint32_t)kGtMaxBits) return ctx->fail(FHH_E_ARG, "gt_cot: bits must be in [1, 4]");
-    if (n == 0) return FHH_OK;
-    if (!gb_bits || !ev_bits || !base_seeds || !base_choice || !gb_share || !ev_share)
-        return ctx->fail(FHH_E_ARG, "gt_cot: NULL argument");
-    if (!(base_choice[0] & 1)) return ctx->fail(FHH_E_ARG, "gt_cot: s is the free-XOR Delta: its bit 0 must be 1");
-    if (n > 0xFFFFFFFFull) return ctx->fail(FHH_E_ARG, "gt_cot: n must fit 32 bits");
-    // the level loop's form of the table (gt_plan.h) at nw = ceil(n / 64); the row-major Z_2^32 kernels'
-    // (k_gt_garble_r32 / k_gt_eval_r32) node values are u32
-    const GtPlan plan = ctx_gt_plan(ctx, GtCaller::kCotHost, bits, 1, 2, ring32, (n + 63) / 64);
-    const bool tm = plan.tile_major;
-    const bool val32 = plan.ring32 && !tm;
-    const uint64_t nw = plan.nw_gc, npad = plan.npad_gc, m = (uint64_t)bits * npad;
-    const uint64_t R = 1ull << bits;
-    std::vector<uint64_t> planes[2];
-    const uint8_t* src[2] = {gb_bits, ev_bits};
-    for (int s = 0; s < 2; s++) {
-        planes[s].assign((size_t)bits * nw + ot_padded(m) / 64, 0);
-        for (uint64_t t = 0; t < n; t++)
-            for (uint32_t j = 0; j < bits; j++)
-                if (src[s][t * bits + j] & 1) planes[s][(size_t)j * nw + t / 64] |= 1ull << (t % 64);
-    }
-    DevBuf dp[2], de, da, dm, dsh;
-    for (int s = 0; s < 2; s++) {
-        HIP_TRY(ctx, dp[s].ensure(planes[s].size() * 8));
-        HIP_TRY(ctx, hipMemcpyAsync(dp[s].p, planes[s].data(), planes[s].size() * 8, hipMemcpyHostToDevice, ctx->stream));
-    }
-    HIP_TRY(ctx, de.ensure(m * 16));
-    HIP_TRY(ctx, da.ensure(m * 16));
-    HIP_TRY(ctx, dm.ensure(std::max<uint64_t>(R - 1, 1) * n * 8));
-    HIP_TRY(ctx, dsh.ensure(2 * n * 8));
-    const uint32_t* rk = nullptr;
-    rc = ot_host_keys(ctx, base_seeds, base_choice, &rk);
-    if (rc) return rc;
-    // 1. the labels OT (mode 4, as fhh_gc_cot_host; b <= 2: mode 5, Q / T left tile-major)
-    OtArgs a{};
-    a.mode = tm ? 5 : 4;
-    a.rk = rk;
-    words_from_bytes(base_choice, a.s);
-    a.choices = dp[1].as<uint32_t>();
-    a.ctr_off = ctr_off;
-    a.sx = de.p;
-    a.out = da.as<uint4>();
-    rc = ot_run(ctx, a, m, nullptr);
-    if (rc) return rc;
-    // 2. the garbled table on the zero labels, 3. its row on the OT'd labels
-    GcArgs g{};
-    g.gb_planes = dp[0].as<uint64_t>();
-    g.ev_planes = dp[1].as<uint64_t>();
-    g.G = 1;
-    g.N = (uint32_t)n;
-    g.nw = (uint32_t)nw;
-    g.bits = bits;
-    g.mask = mask & 1u;
-    words_from_bytes(base_choice, g.delta);
-    g.gate_base = gate_base;
-    g.ev_labels = tm ? ctx->ot_buf[2].as<uint4>() : de.as<uint4>();
-    g.lab_tm = tm ? 1u : 0u;
-    g.ev_ot = 1;
-    g.gt_msgs = dm.as<uint64_t>();
-    g.ring32 = plan.ring32 ? 1u : 0u;
-    g.sh_gb = dsh.as<uint64_t>();
-    HIP_TRY(ctx, launch_gt_garble(g, ctx->stream));
-    g.ev_labels = tm ? ctx->ot_buf[0].as<uint4>() : da.as<uint4>();
-    g.sh_gb = nullptr;
-    g.sh_ev = dsh.as<uint64_t>() + n;
-    HIP_TRY(ctx, launch_gt_eval(g, ctx->stream));
-    if (tm && (ev_zero || ev_active)) {   // the transcript's row-major labels, after the fact (tests only)
-        a.m = m;
-        a.mp = ot_padded(m);
-        a.T = ctx->ot_buf[0].as<uint4>();
-        a.Q = ctx->ot_buf[2].as<uint4>();
-        HIP_TRY(ctx, launch_ot_rows_out(a, true, ctx->stream));
-        HIP_TRY(ctx, launch_ot_rows_out(a, false, ctx->stream));
-    }
-    rc = ctx_sync(ctx);
-    if (rc) return rc;
-    if (val32) {   // u32 values [n] at dsh and at dsh + n u64 (the kernels' sh_gb / sh_ev), zero-extended
-        std::vector<uint32_t> h(n);
-        uint64_t* dst[2] = {gb_share, ev_share};
-        for (int w = 0; w < 2; w++) {
-            HIP_TRY(ctx, hipMemcpy(h.data(), dsh.as<uint64_t>() + w * n, n * 4, hipMemcpyDeviceToHost));
-            for (uint64_t t = 0; t < n; t++) dst[w][t] = h[t];
-        }
-    } else {
-        HIP_TRY(ctx, hipMemcpy(gb_share, dsh.p, n * 8, hipMemcpyDeviceToHost));
-        HIP_TRY(ctx, hipMemcpy(ev_share, dsh.as<uint64_t>() + n, n * 8, hipMemcpyDeviceToHost));
-    }
-    if (msgs && R > 1 && plan.ring32) {   // SoA [R-1][n] u32 on the device -> [n][R-1] (zero-extended)
-        std::vector<uint32_t> h((R - 1) * n);
-        HIP_TRY(ctx, hipMemcpy(h.data(), dm.p, h.size() * 4, hipMemcpyDeviceToHost));
-        for (uint64_t r = 0; r + 1 < R; r++)
-            for (uint64_t t = 0; t < n; t++) msgs[t * (R - 1) + r] = h[r * n + t];
-    } else if (msgs && R > 1) {   // SoA [R-1][n] on the device -> [n][R-1]
-        std::vector<uint64_t> h((R - 1) * n);
-        HIP_TRY(ctx, hipMemcpy(h.data(), dm.p, h.size() * 8, hipMemcpyDeviceToHost));
-        for (uint64_t r = 0; r + 1 < R; r++)
-            for (uint64_t t = 0; t < n; t++) msgs[t * (R - 1) + r] = h[r * n + t];
-    }
-    auto soa_to_aos = [&](const DevBuf& d, uint8_t* dst) -> int {
-        if (!dst) return FHH_OK;
-        std::vector<uint8_t> h((size_t)bits * npad * 16);
-        HIP_TRY(ctx, hipMemcpy(h.data(), d.p, h.size(), hipMemcpyDeviceToHost));
-        for (uint32_t r = 0; r < bits; r++)
-            for (uint64_t t = 0; t < n; t++)
-                std::memcpy(dst + (t * bits + r) * 16, h.data() + ((size_t)r * npad + t) * 16, 16);
-        return FHH_OK;
-    };
-    rc = soa_to_aos(de, ev_zero);
-    if (!rc) rc = soa_to_aos(da, ev_active);
-    return rc;
-}
-
-int fhh_gt_cot_host(fhh_ctx* ctx, uint64_t n, uint32_t bits, const uint8_t* gb_bits, const uint8_t* ev_bits,
-                    uint32_t mask, uint64_t gate_base, const uint8_t base_seeds[128 * 2 * 16],
-                    const uint8_t base_choice[16], uint64_t ctr_off, uint8_t* ev_zero, uint8_t* ev_active,
-                    uint64_t* msgs, uint64_t* gb_share, uint64_t* ev_share) {
-    return gt_cot_host(ctx, n, bits, gb_bits, ev_bits, mask, gate_base, base_seeds, base_choice, ctr_off, ev_zero,
-                       ev_active, msgs, gb_share, ev_share, false);
-}
-
-int fhh_gt_cot_ring32_host(fhh_ctx* ctx, uint64_t n, uint32_t bits, const uint8_t* gb_bits, const uint8_t* ev_bits,
-                           uint32_t mask, uint64_t gate_base, const uint8_t base_seeds[128 * 2 * 16],
-                           const uint8_t base_choice[16], uint64_t ctr_off, uint8_t* ev_zero, uint8_t* ev_active,
-                           uint64_t* msgs, uint64_t* gb_share, uint64_t* ev_share) {
-    return gt_cot_host(ctx, n, bits, gb_bits, ev_bits, mask, gate_base, base_seeds, base_choice, ctr_off, ev_zero,
-                       ev_active, msgs, gb_share, ev_share, true);
-}
-
 }  // extern "C"
 
 // ================================================================================================
@@ -733,19 +309,16 @@ struct PartyState {
     int role = -1;              // 0 garbler / OT sender (server 0), 1 evaluator / OT receiver (server 1)
     int step = 0;               // protocol position (calls must come in order)
     bool last = false;          // tree_crawl_last: FieldElm shares (BlockPair = 2 OTs per test)
-    bool lshare = false;        // r05c (FE levels): the share from the GC output labels, no OT 2
-    bool ltable = false;        // r05d (FE levels, bits <= kGtMaxBits): one garbled table per test
-    bool lring = false;         // form 2 (ltable): the table's shares, messages and node values in Z_2^32 (u32)
-    bool ltm = false;           // r06 (ltable, b <= 2 here: gt_plan.h): the table kernels read the labels OT's
-                                // tile-major Q / T (no row transposes); npad / nw = whole 512-client tiles
+    // the chunk's form (gt_plan.h, set by party_begin): tile_major at b <= 2 only; nw_gc / npad_gc serve both parties
+    GtPlan plan{};
     // C = this instance's children: the chunk [c_off, c_off + C) of the level's level_C children
     // (child_begin / child_count); covered = children whose OTs are finished
     uint64_t c_off = 0, level_C = 0, covered = 0;
     uint32_t level_id = 0;
     bool level_last = false;
     uint32_t level_form = 0;    // the level's first chunk's form: its storage (partials or vals) serves every chunk
-    uint64_t C = 0, n = 0, npad = 0, nw = 0, tests = 0, m1 = 0, m2 = 0;
-    uint32_t bits = 0, mask = 0, per2 = 1;
+    uint64_t C = 0, n = 0, tests = 0, m1 = 0, m2 = 0;
+    uint32_t bits = 0, mask = 0;
     uint32_t s[2][4] = {};      // garbler: the OT-extension sender's base choice words per OT kind
     uint64_t ctr[2] = {0, 0};   // this chunk's row-PRG offsets per OT kind (blocks)
     // per OT kind: the base material of the running session and its next free counter
@@ -759,17 +332,16 @@ struct PartyState {
     DevBuf T, U, Q, Y;          // OT matrices (T / Q private) and messages (U or y)
     DevBuf choices2;            // evaluator: the GC outputs packed as OT 2's choice words
     DevBuf out;                 // evaluator: GC output bytes (eq ^ mask)
-    DevBuf vals;                // the level's node values [level_C][n] (u64, u32 with lring, or a BlockPair at the last level)
-    DevBuf ring_sums;           // lring without lfused: the per-child u64 totals of vals (k_ring32_child_sums)
+    DevBuf vals;                // the level's node values [level_C][n] (u64, u32 with ring32, or a BlockPair at the last level)
+    DevBuf ring_sums;           // ring32 without fused_sums: the per-child u64 totals of vals (k_ring32_child_sums)
     std::vector<uint32_t> rk_host;
     uint64_t bytes_sent = 0;    // this ctx's outgoing message bytes for the level
     uint32_t ss_k = 1;          // r06: 1 IKNP, 2 / 4 SoftSpoken (both OT kinds; fhh_ev_cfg / fhh_gb_cfg.ot_ss_k)
     DevBuf ss_leaf;             // SoftSpoken: this party's GGM leaves
-    // r06 (ltm): the table kernels add this party's node values per child into partials [level_C][4] (the
-    // level loop's layout: garbler slots 0, 1, evaluator 2, 3) instead of storing them in vals, and the
+    // r06 (plan.fused_sums): the table kernels add this party's node values per child into partials [level_C][4]
+    // (the level loop's layout: garbler slots 0, 1, evaluator 2, 3) instead of storing them in vals, and the
     // garble / evaluate calls copy the partials to the host before they return: fhh_party_node_sums then
     // needs no device work (no sums kernel, no values round trip, no extra synchronisation)
-    bool lfused = false;
     DevBuf partials;
     std::vector<uint64_t> partials_host;
 };
@@ -828,38 +400,30 @@ int party_begin(fhh_ctx* ctx, int role, uint64_t child_begin, uint64_t child_cou
     P.tests = P.C * P.n;
     // form 1: the circuit (r05c); form 2: the table over Z_2^32 (the FieldElm level is form 0's). The plane
     // rows and the OT index are both parties' alike: n is public
-    const GtPlan plan = ctx_gt_plan(ctx, GtCaller::kParty, P.bits, last ? 2 : 1, form == 1 ? 3 : 2, form == 2, ctx->nw);
-    P.per2 = plan.per2;
-    P.lshare = plan.lshare;
-    P.ltable = plan.table;
-    P.lring = plan.ring32;
-    P.ltm = plan.tile_major;
-    P.nw = plan.nw_gc;
-    P.npad = plan.npad_gc;
-    P.m1 = P.C * P.bits * P.npad;   // OT index (g bits + j) npad + i: the share planes as choice bits
-    P.m2 = P.lshare ? 0 : P.tests * P.per2;   // OT 2 (the share OT) at the FieldElm level only
+    P.plan = ctx_gt_plan(ctx, GtCaller::kParty, P.bits, last ? 2 : 1, form == 1 ? 3 : 2, form == 2, ctx->nw);
+    P.m1 =P.C * P.bits * P.plan.npad_gc;   // OT index (g bits + j) npad + i: the share planes as choice bits
+    P.m2 = P.plan.lshare ? 0 : P.tests * P.plan.per2;   // OT 2 (the share OT) at the FieldElm level only
     if (b == 0) P.bytes_sent = 0;   // the level's outgoing bytes, over its chunks
     // this server's share planes [C][bits][nw] of the chunk (collect.rs:393-418), zero-padded to the
     // OT's whole choice words (ot_padded(m1) bits)
-    const uint64_t plane_words = P.C * P.bits * P.nw, pad_words = ot_padded(std::max<uint64_t>(P.m1, 1)) / 64;
+    const uint64_t plane_words = P.C * P.bits * P.plan.nw_gc, pad_words = ot_padded(std::max<uint64_t>(P.m1, 1)) / 64;
     HIP_TRY(ctx, P.planes.ensure(std::max(plane_words, pad_words) * 8));
     HIP_TRY(ctx, hipMemsetAsync(P.planes.p, 0, std::max(plane_words, pad_words) * 8, ctx->stream));
     if (P.C) {
         ChildArgs a = ctx_child_args(ctx);
         a.c_off = P.c_off;
         a.c_cnt = P.C;
-        a.plane_nw = (uint32_t)P.nw;
+        a.plane_nw = (uint32_t)P.plan.nw_gc;
         HIP_TRY(ctx, launch_share_planes(a, P.planes.as<uint64_t>(), ctx->stream));
     }
     // the level's node values, one row of n per child (u64 FE, or a BlockPair at the last level); with the
-    // fused sums (ltm) only the per-child partials, zeroed at the level's first chunk
-    P.lfused = plan.fused_sums;
-    if (b == 0 && P.lfused) {
+    // fused sums (tile_major) only the per-child partials, zeroed at the level's first chunk
+    if (b == 0 && P.plan.fused_sums) {
         HIP_TRY(ctx, P.partials.ensure(std::max<uint64_t>(LC, 1) * 4 * 8));
         HIP_TRY(ctx, hipMemsetAsync(P.partials.p, 0, std::max<uint64_t>(LC, 1) * 4 * 8, ctx->stream));
         P.partials_host.assign(std::max<uint64_t>(LC, 1) * 4, 0);
     } else if (b == 0) {
-        HIP_TRY(ctx, P.vals.ensure(std::max<uint64_t>(LC * P.n * P.per2, 1) * (P.last ? 16 : P.lring ? 4 : 8)));
+        HIP_TRY(ctx, P.vals.ensure(std::max<uint64_t>(LC * P.n * P.plan.per2, 1) * (P.last ? 16 : P.plan.ring32 ? 4 : 8)));
     }
     return FHH_OK;
 }
@@ -867,7 +431,7 @@ int party_begin(fhh_ctx* ctx, int role, uint64_t child_begin, uint64_t child_cou
 // the fused partials of the level so far, to the host (each chunk's call copies the whole accumulating
 // array; after the level's last chunk the host copy is complete)
 int party_partials_to_host(fhh_ctx* ctx, PartyState& P) {
-    if (!P.lfused || P.level_C == 0) return FHH_OK;
+    if (!P.plan.fused_sums || P.level_C == 0) return FHH_OK;
     HIP_TRY(ctx, hipMemcpyAsync(P.partials_host.data(), P.partials.p, P.level_C * 4 * 8, hipMemcpyDeviceToHost,
                                 ctx->stream));
     return FHH_OK;
@@ -933,8 +497,8 @@ int party_ot_buffers(fhh_ctx* ctx, PartyState& P, uint64_t m, bool receiver, boo
 }
 
 uint64_t gc_bytes(const PartyState& P) {
-    if (P.ltable) return P.tests * (((uint64_t)1 << P.bits) - 1) * (P.lring ? 4 : 8);   // rows 1 .. 2^bits - 1, 8 B (Z_2^32: 4 B) each
-    return P.tests * ((uint64_t)2 * (P.bits - 1) * 16 + 1 + (P.lshare ? 8 : 0));
+    if (P.plan.table) return P.tests * (((uint64_t)1 << P.bits) - 1) * (P.plan.ring32 ? 4 : 8);   // rows 1 .. 2^bits - 1, 8 B (Z_2^32: 4 B) each
+    return P.tests * ((uint64_t)2 * (P.bits - 1) * 16 + 1 + (P.plan.lshare ? 8 : 0));
 }
 uint64_t y2_bytes(const PartyState& P) { return P.m2 * (P.last ? 16 : 8); }
 
@@ -952,9 +516,9 @@ void gc_layout(const PartyState& P, uint8_t* base, GcArgs& g) {
     const uint64_t t = P.tests, tb = (uint64_t)2 * (P.bits - 1) * t * 16;
     g.tables = reinterpret_cast<uint4*>(base);
     g.gb_labels = nullptr;
-    g.sh_y = P.lshare ? reinterpret_cast<uint64_t*>(base + tb) : nullptr;
-    g.decode = base + tb + (P.lshare ? 8 * t : 0);
-    if (P.ltable) {   // r05d: the gc message is the garbled table's rows 1 .. 2^bits - 1 (SoA, u64; lring: u32)
+    g.sh_y = P.plan.lshare ? reinterpret_cast<uint64_t*>(base + tb) : nullptr;
+    g.decode = base + tb + (P.plan.lshare ? 8 * t : 0);
+    if (P.plan.table) {   // r05d: the gc message is the garbled table's rows 1 .. 2^bits - 1 (SoA, u64; ring32: u32)
         g.tables = nullptr;
         g.sh_y = nullptr;
         g.decode = nullptr;
@@ -964,14 +528,14 @@ void gc_layout(const PartyState& P, uint8_t* base, GcArgs& g) {
 
 // this chunk's rows of the level's node values (u64 FE, u32 in Z_2^32, or a BlockPair at the last level)
 uint8_t* party_vals(PartyState& P) {
-    return P.vals.as<uint8_t>() + P.c_off * P.n * P.per2 * (P.last ? 16 : P.lring ? 4 : 8);
+    return P.vals.as<uint8_t>() + P.c_off * P.n * P.plan.per2 * (P.last ? 16 : P.plan.ring32 ? 4 : 8);
 }
 
 // form 2: this ctx's per-child totals of the level's Z_2^32 node values, added into acc [level_C] (u64; the
 // caller reduces mod 2^32 once): the fused partials' low sums (b <= 2), or k_ring32_child_sums over vals
 int party_ring_totals(fhh_ctx* ctx, PartyState& P, std::vector<uint64_t>& acc) {
     const uint64_t LC = P.level_C;
-    if (P.lfused) {
+    if (P.plan.fused_sums) {
         const int k0 = P.role == 0 ? 0 : 2;
         for (uint64_t c = 0; c < LC; c++) acc[c] += P.partials_host[4 * c + k0] + (P.partials_host[4 * c + k0 + 1] << 32);
         return FHH_OK;
@@ -1015,23 +579,23 @@ int fhh_ev_ot_labels(fhh_ctx* ctx, const fhh_ev_cfg* cfg, const uint8_t** u_dev,
     // (kind 1, the share OT, at the FieldElm level only: the FE levels' share rides on the GC, r05c)
     party_session(P, 0, &cfg->base_pairs[0][0][0][0], 128 * 32, P.m1);
     rc = party_keys(ctx, P, 0, &cfg->base_pairs[0][0][0][0], nullptr);
-    if (!rc && !P.lshare) {
+    if (!rc && !P.plan.lshare) {
         party_session(P, 1, &cfg->base_pairs[1][0][0][0], 128 * 32, P.m2);
         rc = party_keys(ctx, P, 1, &cfg->base_pairs[1][0][0][0], nullptr);
     }
     if (rc) return rc;
     rc = party_ot_buffers(ctx, P, P.m1, true);
     if (rc) return rc;
-    if (!P.ltm) HIP_TRY(ctx, P.labels.ensure(std::max<uint64_t>(P.m1, 1) * 16));
+    if (!P.plan.tile_major) HIP_TRY(ctx, P.labels.ensure(std::max<uint64_t>(P.m1, 1) * 16));
     if (P.m1) {   // OT 1's receiver: choice bits = this server's share planes as they stand
         OtArgs a = party_ot(P, 0, P.m1);
-        a.mode = P.ltm ? 5 : 4;
+        a.mode = P.plan.tile_major ? 5 : 4;
         a.choices = P.planes.as<uint32_t>();
-        a.out = P.ltm ? nullptr : P.labels.as<uint4>();
+        a.out = P.plan.tile_major ? nullptr : P.labels.as<uint4>();
         HIP_TRY(ctx, party_ggm(P, a, true, ctx->stream));
         HIP_TRY(ctx, launch_ot_recv_expand(a, ctx->stream));        // T, U
         // its active labels t_j: row-major for the circuit; the r06 table reads T tile-major
-        if (!P.ltm) HIP_TRY(ctx, launch_ot_rows_out(a, false, ctx->stream));
+        if (!P.plan.tile_major) HIP_TRY(ctx, launch_ot_rows_out(a, false, ctx->stream));
     }
     rc = ctx_sync(ctx);
     if (rc) return rc;
@@ -1061,7 +625,7 @@ int fhh_gb_ot_labels(fhh_ctx* ctx, const fhh_gb_cfg* cfg, const uint8_t* u_dev, 
         return ctx->fail(FHH_E_ARG, "gb_ot_labels: the labels base OTs' s is the free-XOR Delta: its bit 0 must be 1");
     // the OT kinds' sender schedules and session counters (OtSender::init, collect.rs:454): kind 1 (the
     // share OT) at the FieldElm level only (r05c)
-    for (int w = 0; w < (P.lshare ? 1 : 2); w++) {
+    for (int w = 0; w < (P.plan.lshare ? 1 : 2); w++) {
         std::vector<uint8_t> mat((size_t)128 * 16 + 16);
         std::memcpy(mat.data(), &cfg->base_chosen[w][0][0], 128 * 16);
         std::memcpy(mat.data() + 128 * 16, cfg->base_choice[w], 16);
@@ -1073,13 +637,13 @@ int fhh_gb_ot_labels(fhh_ctx* ctx, const fhh_gb_cfg* cfg, const uint8_t* u_dev, 
     // the garbling arguments of the chunk (multiple_gb_equality_test, equalitytest.rs:25-65); the
     // evaluator's zero labels are OT 1's sender messages, at the OT index of its choice bits
     HIP_TRY(ctx, P.gc.ensure(std::max<uint64_t>(gc_bytes(P), 1)));
-    if (!P.ltm) HIP_TRY(ctx, P.labels.ensure(std::max<uint64_t>(P.m1, 1) * 16));
+    if (!P.plan.tile_major) HIP_TRY(ctx, P.labels.ensure(std::max<uint64_t>(P.m1, 1) * 16));
     rc = party_ot_buffers(ctx, P, P.m1, false, false);
     if (rc) return rc;
     fhh_gc_batch gb{};
     gb.groups = P.C;
     gb.clients = (uint32_t)P.n;
-    gb.words = (uint32_t)P.nw;
+    gb.words = (uint32_t)P.plan.nw_gc;
     gb.bits = P.bits;
     gb.mask = P.mask;
     std::memcpy(gb.delta, cfg->base_choice[0], 16);   // Delta = the labels session's s
@@ -1088,32 +652,32 @@ int fhh_gb_ot_labels(fhh_ctx* ctx, const fhh_gb_cfg* cfg, const uint8_t* u_dev, 
     gb.ev_planes_dev = P.planes.as<uint64_t>();   // not read: the evaluator's labels go by OT
     gb.tables_dev = P.gc.as<uint8_t>();
     gb.gb_labels_dev = P.gc.as<uint8_t>();
-    gb.ev_labels_dev = P.ltm ? P.Q.as<uint8_t>() : P.labels.as<uint8_t>();   // r06: the tile-major Q itself
+    gb.ev_labels_dev = P.plan.tile_major ? P.Q.as<uint8_t>() : P.labels.as<uint8_t>();   // r06: the tile-major Q itself
     gb.decode_dev = P.gc.as<uint8_t>();
     gb.out_dev = P.gc.as<uint8_t>();
     rc = gc_args(ctx, &gb, P.g);
     if (rc) return rc;
     gc_layout(P, P.gc.as<uint8_t>(), P.g);
     P.g.ev_ot = 1;
-    P.g.lab_tm = P.ltm ? 1u : 0u;
-    P.g.ring32 = P.lring ? 1u : 0u;
+    P.g.lab_tm = P.plan.tile_major ? 1u : 0u;
+    P.g.ring32 = P.plan.ring32 ? 1u : 0u;
     P.g.out = nullptr;
     // r05c: the garbler's node values r1 straight into the level's rows (the y it forms travels in gc);
-    // r06 (ltm): added per child into the partials instead
-    P.g.sh_gb = P.lshare && !P.lfused ? reinterpret_cast<uint64_t*>(party_vals(P)) : nullptr;
-    P.g.node_partials = P.lfused ? P.partials.as<uint64_t>() : nullptr;
+    // r06 (tile_major): added per child into the partials instead
+    P.g.sh_gb = P.plan.lshare && !P.plan.fused_sums ? reinterpret_cast<uint64_t*>(party_vals(P)) : nullptr;
+    P.g.node_partials = P.plan.fused_sums ? P.partials.as<uint64_t>() : nullptr;
     P.g.node_off = P.c_off;
     // OT 1 as the IKNP correlation (gb_set_fancy_inputs, equalitytest.rs:67-82): q_j is the evaluator's
     // zero label of its share bit j, q_j ^ s its one label, and s = Delta: nothing to send back
     if (P.m1) {
         OtArgs a = party_ot(P, 0, P.m1);
-        a.mode = P.ltm ? 5 : 4;
+        a.mode = P.plan.tile_major ? 5 : 4;
         a.U = const_cast<uint4*>(reinterpret_cast<const uint4*>(u_dev));
         for (int c = 0; c < 4; c++) a.s[c] = P.s[0][c];
-        a.sx = P.ltm ? nullptr : P.labels.p;
+        a.sx = P.plan.tile_major ? nullptr : P.labels.p;
         HIP_TRY(ctx, party_ggm(P, a, false, ctx->stream));
         HIP_TRY(ctx, launch_ot_send_expand(a, ctx->stream));      // Q from U
-        if (!P.ltm) HIP_TRY(ctx, launch_ot_rows_out(a, true, ctx->stream));   // the zero labels q_j (the circuit)
+        if (!P.plan.tile_major) HIP_TRY(ctx, launch_ot_rows_out(a, true, ctx->stream));   // the zero labels q_j (the circuit)
     }
     rc = ctx_sync(ctx);
     if (rc) return rc;
@@ -1131,7 +695,7 @@ int fhh_gb_garble(fhh_ctx* ctx, const uint8_t** gc_msg_dev, uint64_t* gc_msg_byt
     PartyState* Pp = ctx->party;
     if (!Pp || Pp->role != 0 || Pp->step != 1) return ctx->fail(FHH_E_STATE, "gb_garble: call after fhh_gb_ot_labels");
     PartyState& P = *Pp;
-    if (P.tests) HIP_TRY(ctx, P.ltable ? launch_gt_garble(P.g, ctx->stream) : launch_gc_garble(P.g, ctx->stream));
+    if (P.tests) HIP_TRY(ctx, P.plan.table ? launch_gt_garble(P.g, ctx->stream) : launch_gc_garble(P.g, ctx->stream));
     rc = party_partials_to_host(ctx, P);
     if (rc) return rc;
     rc = ctx_sync(ctx);
@@ -1166,26 +730,26 @@ int fhh_ev_evaluate(fhh_ctx* ctx, const uint8_t* gc_msg_dev, uint64_t gc_len, co
     GcArgs g{};
     g.G = P.C;
     g.N = (uint32_t)P.n;
-    g.nw = (uint32_t)P.nw;
+    g.nw = (uint32_t)P.plan.nw_gc;
     g.bits = P.bits;
     g.gate_base = party_gate_base(P);
     gc_layout(P, const_cast<uint8_t*>(gc_msg_dev), g);
-    g.ev_labels = P.ltm ? P.T.as<uint4>() : P.labels.as<uint4>();   // r06: the tile-major T itself
-    g.lab_tm = P.ltm ? 1u : 0u;
-    g.ring32 = P.lring ? 1u : 0u;
+    g.ev_labels = P.plan.tile_major ? P.T.as<uint4>() : P.labels.as<uint4>();   // r06: the tile-major T itself
+    g.lab_tm = P.plan.tile_major ? 1u : 0u;
+    g.ring32 = P.plan.ring32 ? 1u : 0u;
     g.ev_ot = 1;
     g.out = P.out.as<uint8_t>();
-    if (P.lfused) {   // r06: added per child into the partials
+    if (P.plan.fused_sums) {   // r06: added per child into the partials
         g.node_partials = P.partials.as<uint64_t>();
         g.node_off = P.c_off;
-    } else if (P.lshare) {
+    } else if (P.plan.lshare) {
         // r05c: its node value from its output label and the gc message's y, straight into the rows
         g.sh_ev = reinterpret_cast<uint64_t*>(party_vals(P));
     } else {
         g.out_packed = P.choices2.as<uint32_t>();
-        g.out_dup = P.per2;
+        g.out_dup = P.plan.per2;
     }
-    if (P.tests) HIP_TRY(ctx, P.ltable ? launch_gt_eval(g, ctx->stream) : launch_gc_eval(g, ctx->stream));
+    if (P.tests) HIP_TRY(ctx, P.plan.table ? launch_gt_eval(g, ctx->stream) : launch_gc_eval(g, ctx->stream));
     rc = party_partials_to_host(ctx, P);
     if (rc) return rc;
     // 3. OT 2's receiver: choice = the GC output (collect.rs:461-471); T and U reused
@@ -1294,11 +858,11 @@ int fhh_party_node_sums(fhh_ctx* ctx, void* sums_a, void* sums_b) {
             last = P->last;
             // one path for all: the fused host partials, or the stored values (a shard of the other kind has
             // nothing valid in the buffer that path reads)
-            if (fused >= 0 && fused != (int)P->lfused) return ctx->fail(FHH_E_STATE, "party_node_sums: shards disagree");
-            fused = P->lfused;
+            if (fused >= 0 && fused != (int)P->plan.fused_sums) return ctx->fail(FHH_E_STATE, "party_node_sums: shards disagree");
+            fused = P->plan.fused_sums;
             // FE or Z_2^32 shares (forms 0 and 2 are both fused at d = 1: the sums' group must agree too)
-            if (ring >= 0 && ring != (int)P->lring) return ctx->fail(FHH_E_STATE, "party_node_sums: shards disagree");
-            ring = P->lring;
+            if (ring >= 0 && ring != (int)P->plan.ring32) return ctx->fail(FHH_E_STATE, "party_node_sums: shards disagree");
+            ring = P->plan.ring32;
             v[(size_t)k] = P->vals.p;
             fused_shards.push_back(P);
             ring_ctxs.push_back(sh);
@@ -1321,7 +885,7 @@ int fhh_party_node_sums(fhh_ctx* ctx, void* sums_a, void* sums_b) {
             const uint64_t LC = fused_shards[0]->level_C;
             std::vector<uint64_t> h(LC * 2, 0);
             for (PartyState* P : fused_shards) {
-                if (!P->lfused || P->level_C != LC) return ctx->fail(FHH_E_STATE, "party_node_sums: shards disagree");
+                if (!P->plan.fused_sums || P->level_C != LC) return ctx->fail(FHH_E_STATE, "party_node_sums: shards disagree");
                 const int k0 = P->role == 0 ? 0 : 2;
                 for (uint64_t c = 0; c < LC; c++) {
                     h[2 * c] += P->partials_host[4 * c + k0];
@@ -1340,7 +904,7 @@ int fhh_party_node_sums(fhh_ctx* ctx, void* sums_a, void* sums_b) {
     if (!Pp || Pp->step != 3 || Pp->covered != Pp->level_C)
         return ctx->fail(FHH_E_STATE, "party_node_sums: the level's OTs are not finished for every child");
     PartyState& P = *Pp;
-    if (P.lring) {   // form 2: the party's sum mod 2^32, zero-extended
+    if (P.plan.ring32) {   // form 2: the party's sum mod 2^32, zero-extended
         std::vector<uint64_t> acc(P.level_C, 0);
         int rc = party_ring_totals(ctx, P, acc);
         if (rc) return rc;
@@ -1349,7 +913,7 @@ int fhh_party_node_sums(fhh_ctx* ctx, void* sums_a, void* sums_b) {
             for (uint64_t c = 0; c < P.level_C; c++) sums[c] = acc[c] & 0xFFFFFFFFull;
         return FHH_OK;
     }
-    if (P.lfused) {   // r06: the partials the garble / evaluate calls copied to the host
+    if (P.plan.fused_sums) {   // r06: the partials the garble / evaluate calls copied to the host
         const int k0 = P.role == 0 ? 0 : 2;
         uint64_t* sums = static_cast<uint64_t*>(sums_a);
         if (sums)

@@ -1,5 +1,5 @@
-// Internal interface between the host engine (fhh_host.cpp) and the HIP kernels
-// (fhh_kernels.hip). Not part of the public C ABI (include/fhh.h).
+// Internal interface between the host engine (the .cpp sources, fhh_engine.h) and the HIP kernels
+// (the .hip sources). Not part of the public C ABI (include/fhh.h).
 //
 // Device layout of one server's keys and evaluation states (SoA, lane = client):
 //   npad = 64 * nw clients (padded), K = 2*d keys per client, kk = 2*j + side

@@ -1,14 +1,10 @@
 // The form a level's GC equality test takes: which kernels (half-gates circuit or one garbled table per
 // test), on which layout of the labels OT's output, with which plane pitch, and who adds the node values
-// per child. Decided here for the three host callers (the device level loop in fhh_host.cpp, gt_cot_host
-// and party_begin in fhh_gcot.cpp). Host-only, no HIP: compiles with any C++17 compiler; host self-test
-// tests/host/gt_plan_host_test.cpp.
+// per child. Decided here for the three host callers (the device level loop in fhh_sim_crawl.cpp, gt_cot_host
+// in fhh_gcot_harness.cpp and party_begin in fhh_gcot.cpp). Host-only, no HIP: compiles with any C++17
+// compiler; host self-test tests/host/gt_plan_host_test.cpp.
 #pragma once
 #include <cstdint>
-
-#ifndef FHH_GT_FUSED_SUMS
-#define FHH_GT_FUSED_SUMS 1   // r06: the tile-major table kernels add the node values per child themselves
-#endif
 
 namespace fhh {
 
@@ -68,11 +64,10 @@ inline GtPlan gt_plan(GtCaller who, uint32_t bits, uint32_t kind, uint32_t gc, b
     // width serve the level loop and fhh_gt_cot*_host only)
     if (who == GtCaller::kParty && bits > (uint32_t)kGtTmPadBits) p.tile_major = false;
     p.windows = p.tile_major && bits > (uint32_t)kGtTmPadBits;
-    // FHH_GT_FUSED_SUMS is the loop's switch: the party ABI has no unfused tile-major path, and
-    // fhh_gt_cot*_host returns every test's shares
-    p.fused_sums = p.tile_major && (who == GtCaller::kParty || (who == GtCaller::kLoop && FHH_GT_FUSED_SUMS));
-    // (the loop sums Z_2^32 values only fused or through k_ring32_child_partials, both behind the switch)
-    p.ring32 = ring_req && p.table && bits <= (uint32_t)kGtTmMaxBits && (who != GtCaller::kLoop || FHH_GT_FUSED_SUMS);
+    // r06: the tile-major table kernels add the node values per child themselves (fhh_gt_cot*_host returns every
+    // test's shares)
+    p.fused_sums = p.tile_major && who != GtCaller::kCotHost;
+    p.ring32 = ring_req && p.table && bits <= (uint32_t)kGtTmMaxBits;
     p.nw_gc = p.tile_major && !p.windows ? (nw + 7) / 8 * 8 : nw;
     p.npad_gc = 64 * p.nw_gc;
     p.per2 = kind == 1 ? 1 : 2;
