@@ -447,9 +447,35 @@ __device__ __forceinline__ uint64_t fe_dec(uint64_t v) { return v ? v - 1 : kOtF
 #define FHH_GT_EVAL_U 2
 #endif
 
+// The share domain of the row-major table (b = 3, 4, the d = 2 tests; at b <= 2 every table is tile-major,
+// gt_plan.h): the field (oracle orc_gt_garble / orc_gt_eval), or Z_2^32 (GcArgs::ring32 without lab_tm; oracle
+// orc_gt_garble_ring32 / orc_gt_eval_ring32, the arithmetic of k_gt_garble_tm's RING branch). Row keys, tweak,
+// colours and rstar are the same in both. T is the type of a message and of a node value: gt_msgs is SoA
+// [2^b - 1][n] T and sh_gb / sh_ev are [n] T, whatever GcArgs declares them. In Z_2^32 a row starts at byte
+// 4 r n and n may be odd, so every message and value moves by a 4-B access.
+template <bool RING>
+struct GtShare {   // FE: row 0's value is H(K_0) mod p, rows 1 .. 2^b - 1 send lo64(H(K_r)) ^ pair[o_r]
+    using T = uint64_t;
+    static __device__ __forceinline__ T pad(const uint32_t (&h)[4]) { return (uint64_t)h[0] | ((uint64_t)h[1] << 32); }
+    static __device__ __forceinline__ T row0(const uint32_t (&h)[4]) {
+        return ot_fe_of_u128(pad(h), (uint64_t)h[2] | ((uint64_t)h[3] << 32));
+    }
+    static __device__ __forceinline__ T inc(T v) { return fe_inc(v); }
+    static __device__ __forceinline__ T dec(T v) { return fe_dec(v); }
+};
+template <>
+struct GtShare<true> {   // Z_2^32: row 0's value is lo32(H(K_0)), the pair (v, v +- 1 mod 2^32), messages lo32 ^ pair
+    using T = uint32_t;
+    static __device__ __forceinline__ T pad(const uint32_t (&h)[4]) { return h[0]; }
+    static __device__ __forceinline__ T row0(const uint32_t (&h)[4]) { return h[0]; }
+    static __device__ __forceinline__ T inc(T v) { return v + 1u; }
+    static __device__ __forceinline__ T dec(T v) { return v - 1u; }
+};
 
-template <int B>
+template <int B, bool RING>
 __global__ __launch_bounds__(kGcThreads) void k_gt_garble(GcArgs a) {
+    using Sh = GtShare<RING>;
+    using T = typename Sh::T;
     __shared__ uint32_t tbl_gc[GcTab::kWords];
     if ((uint64_t)blockIdx.x * kGcThreads >= gc_active(a)) return;   // no tests: skip the table fill
     gc_fill(tbl_gc);
@@ -460,6 +486,8 @@ __global__ __launch_bounds__(kGcThreads) void k_gt_garble(GcArgs a) {
     constexpr int U = FHH_GT_GARBLE_U;       // tests per lane per pass
     const uint64_t n = a.G * a.N;
     const uint64_t Npad = (uint64_t)a.nw * 64;
+    T* msgs = reinterpret_cast<T*>(a.gt_msgs);
+    T* vals = reinterpret_cast<T*>(a.sh_gb);
     uint32_t Dk[B][4];   // sigma^k(Delta)
 #pragma unroll
     for (int c = 0; c < 4; c++) Dk[0][c] = a.delta[c];
@@ -517,7 +545,7 @@ __global__ __launch_bounds__(kGcThreads) void k_gt_garble(GcArgs a) {
             S[u][0] ^= (uint32_t)tw;
             S[u][1] ^= (uint32_t)(tw >> 32);
         }
-        uint64_t p0[U], p1[U];
+        T p0[U], p1[U];
 #pragma unroll
         for (uint32_t pass = 0; pass < R / NB; pass++) {
             uint32_t h[U * NB][4];
@@ -543,16 +571,14 @@ __global__ __launch_bounds__(kGcThreads) void k_gt_garble(GcArgs a) {
                 for (int j = 0; j < NB; j++) {
                     const uint32_t r = pass * NB + j;
                     const uint32_t o = (uint32_t)(r == rstar) ^ a.mask;
-                    const uint32_t* hj = h[u * NB + j];
-                    const uint64_t hl = (uint64_t)hj[0] | ((uint64_t)hj[1] << 32);
-                    if (r == 0) {   // row 0's value pair[o_0] is H(K_0) mod p: it fixes v
-                        const uint64_t hv = ot_fe_of_u128(hl, (uint64_t)hj[2] | ((uint64_t)hj[3] << 32));
-                        const uint64_t v = o == 0 ? hv : (a.mask ? fe_dec(hv) : fe_inc(hv));
+                    if (r == 0) {   // row 0's value pair[o_0] comes from H(K_0) alone: it fixes v
+                        const T hv = Sh::row0(h[u * NB + j]);
+                        const T v = o == 0 ? hv : (a.mask ? Sh::dec(hv) : Sh::inc(hv));
                         p0[u] = v;
-                        p1[u] = a.mask ? fe_inc(v) : fe_dec(v);
-                        if (t < n_act) a.sh_gb[t] = a.mask ? fe_inc(v) : v;   // r1 = v + mask
+                        p1[u] = a.mask ? Sh::inc(v) : Sh::dec(v);
+                        if (t < n_act) vals[t] = a.mask ? Sh::inc(v) : v;   // r1 = v + mask
                     } else if (t < n_act) {
-                        a.gt_msgs[(uint64_t)(r - 1) * n + t] = hl ^ (o ? p1[u] : p0[u]);
+                        msgs[(uint64_t)(r - 1) * n + t] = Sh::pad(h[u * NB + j]) ^ (o ? p1[u] : p0[u]);
                     }
                 }
             }
@@ -560,8 +586,10 @@ __global__ __launch_bounds__(kGcThreads) void k_gt_garble(GcArgs a) {
     }
 }
 
-template <int B>
+template <int B, bool RING>
 __global__ __launch_bounds__(kGcThreads) void k_gt_eval(GcArgs a) {
+    using Sh = GtShare<RING>;
+    using T = typename Sh::T;
     __shared__ uint32_t tbl_gc[GcTab::kWords];
     if ((uint64_t)blockIdx.x * kGcThreads >= gc_active(a)) return;
     gc_fill(tbl_gc);
@@ -570,146 +598,8 @@ __global__ __launch_bounds__(kGcThreads) void k_gt_eval(GcArgs a) {
     const uint64_t n = a.G * a.N;
     const uint64_t Npad = (uint64_t)a.nw * 64;
     const uint64_t n_act = gc_active(a);
-    // U tests per lane per pass (U AES blocks in flight)
-    constexpr int U = FHH_GT_EVAL_U;
-    const uint64_t stride = (uint64_t)gridDim.x * kGcThreads;
-    for (uint64_t t0 = (uint64_t)blockIdx.x * kGcThreads + threadIdx.x; t0 < n_act; t0 += U * stride) {
-        uint32_t h[U][4], row[U];
-        uint64_t tt[U];
-#pragma unroll
-        for (int u = 0; u < U; u++) {
-            const uint64_t t = t0 + u * stride;
-            tt[u] = t;
-            const uint64_t tc = t < n_act ? t : t0;   // a valid test for the padding block
-            const uint64_t g = tc / a.N;
-            const uint32_t i = (uint32_t)(tc - g * a.N);
-            const uint64_t tw = a.gate_base + a.g_off * a.N + tc;
-            uint32_t S[4] = {0u, 0u, 0u, 0u}, r = 0;
-#pragma unroll
-            for (int k = B - 1; k >= 0; k--) {
-                uint32_t z[4];
-                ld_blk(a.ev_labels, g * B + k, Npad, i, z);   // t_k, z_k's active label
-                gf_dbl(S);
-#pragma unroll
-                for (int c = 0; c < 4; c++) S[c] ^= z[c];
-                r |= (z[0] & 1u) << k;
-            }
-            S[0] ^= (uint32_t)tw;
-            S[1] ^= (uint32_t)(tw >> 32);
-#pragma unroll
-            for (int c = 0; c < 4; c++) h[u][c] = S[c];
-            row[u] = r;
-        }
-        aes0_mmo_tab<DevOpsX, GcTab, U>(h, tbl_gc, b0, b1);
-#pragma unroll
-        for (int u = 0; u < U; u++) {
-            const uint64_t t = tt[u];
-            if (t >= n_act) continue;
-            const uint64_t hl = (uint64_t)h[u][0] | ((uint64_t)h[u][1] << 32);
-            a.sh_ev[t] = row[u] ? (hl ^ a.gt_msgs[(uint64_t)(row[u] - 1) * n + t])
-                                : ot_fe_of_u128(hl, (uint64_t)h[u][2] | ((uint64_t)h[u][3] << 32));
-        }
-    }
-}
-
-// ---- the row-major table over Z_2^32 (GcArgs::ring32 without lab_tm: b = 3, 4, the d = 2 tests) ----
-// k_gt_garble / k_gt_eval with the shares in Z_2^32 (oracle orc_gt_garble_ring32 / orc_gt_eval_ring32,
-// the arithmetic of k_gt_garble_tm's RING branch): row keys, tweak, colours and rstar as there; row 0's
-// value is lo32(H(K_0)), the pair (v, v +- 1 mod 2^32), rows 1 .. 2^b - 1 send lo32(H(K_r)) ^ pair[o_r] as
-// u32, SoA [2^b - 1][n]; the node values are u32 too (sh_gb / sh_ev read as uint32_t [n]). A row starts
-// at byte 4 r n and n may be odd, so every message and value moves by a 4-B access. Kernels of their own:
-// the FE instantiations above keep their code and register budgets.
-template <int B>
-__global__ __launch_bounds__(kGcThreads) void k_gt_garble_r32(GcArgs a) {
-    __shared__ uint32_t tbl_gc[GcTab::kWords];
-    if ((uint64_t)blockIdx.x * kGcThreads >= gc_active(a)) return;   // no tests: skip the table fill
-    gc_fill(tbl_gc);
-    uint32_t b0, b1;
-    GcTab::bases(threadIdx.x & 63, b0, b1);
-    constexpr uint32_t R = 1u << B;
-    constexpr int NB = R < 4 ? (int)R : 4;   // rows per AES pass
-    const uint64_t n = a.G * a.N;
-    const uint64_t Npad = (uint64_t)a.nw * 64;
-    uint32_t* msgs = reinterpret_cast<uint32_t*>(a.gt_msgs);
-    uint32_t* vals = reinterpret_cast<uint32_t*>(a.sh_gb);
-    uint32_t Dk[B][4];   // sigma^k(Delta)
-#pragma unroll
-    for (int c = 0; c < 4; c++) Dk[0][c] = a.delta[c];
-#pragma unroll
-    for (int k = 1; k < B; k++) {
-#pragma unroll
-        for (int c = 0; c < 4; c++) Dk[k][c] = Dk[k - 1][c];
-        gf_dbl(Dk[k]);
-    }
-    const uint64_t n_act = gc_active(a);
-    const uint64_t stride = (uint64_t)gridDim.x * kGcThreads;
-    for (uint64_t t = (uint64_t)blockIdx.x * kGcThreads + threadIdx.x; t < n_act; t += stride) {
-        const uint64_t g = t / a.N;
-        const uint32_t i = (uint32_t)(t - g * a.N);
-        const uint64_t tw = a.gate_base + a.g_off * a.N + t;   // the test's index in the whole level
-        uint32_t S[4] = {0u, 0u, 0u, 0u}, col = 0;
-#pragma unroll
-        for (int k = B - 1; k >= 0; k--) {   // Horner: S = sigma(S) ^ Z_k
-            uint32_t z[4];
-            ld_blk(a.ev_labels, g * B + k, Npad, i, z);   // E_k, the labels OT's q
-            const uint32_t xb = plane_bit(a.gb_planes, a.g_off + g, B, k, a.nw, i);
-            gf_dbl(S);
-#pragma unroll
-            for (int c = 0; c < 4; c++) {
-                z[c] ^= xb ? 0u : a.delta[c];   // Z_k = E_k ^ (x_k ? 0 : Delta)
-                S[c] ^= z[c];
-            }
-            col |= (z[0] & 1u) << k;
-        }
-        S[0] ^= (uint32_t)tw;
-        S[1] ^= (uint32_t)(tw >> 32);
-        const uint32_t rstar = ~col & (R - 1);   // the row whose z are all 1 (eq = 1)
-        uint32_t p0 = 0, p1 = 0;
-#pragma unroll
-        for (uint32_t pass = 0; pass < R / NB; pass++) {
-            uint32_t h[NB][4];
-#pragma unroll
-            for (int j = 0; j < NB; j++) {
-                const uint32_t flip = (pass * NB + j) ^ col;   // z_k of the row = bit k of r ^ col
-#pragma unroll
-                for (int c = 0; c < 4; c++) {
-                    uint32_t w = S[c];
-#pragma unroll
-                    for (int k = 0; k < B; k++) w ^= ((flip >> k) & 1u) ? Dk[k][c] : 0u;
-                    h[j][c] = w;
-                }
-            }
-            aes0_mmo_tab<DevOpsX, GcTab, NB>(h, tbl_gc, b0, b1);   // cr_hash: pi(K) ^ K
-#pragma unroll
-            for (int j = 0; j < NB; j++) {
-                const uint32_t r = pass * NB + j;
-                const uint32_t o = (uint32_t)(r == rstar) ^ a.mask;
-                if (r == 0) {   // row 0's value pair[o_0] is lo32(H(K_0)): it fixes v
-                    const uint32_t h32 = h[0][0];
-                    const uint32_t v = o == 0 ? h32 : (a.mask ? h32 - 1u : h32 + 1u);
-                    p0 = v;
-                    p1 = a.mask ? v + 1u : v - 1u;
-                    vals[t] = a.mask ? v + 1u : v;   // r1 = v + mask
-                } else {
-                    msgs[(uint64_t)(r - 1) * n + t] = h[j][0] ^ (o ? p1 : p0);
-                }
-            }
-        }
-    }
-}
-
-template <int B>
-__global__ __launch_bounds__(kGcThreads) void k_gt_eval_r32(GcArgs a) {
-    __shared__ uint32_t tbl_gc[GcTab::kWords];
-    if ((uint64_t)blockIdx.x * kGcThreads >= gc_active(a)) return;
-    gc_fill(tbl_gc);
-    uint32_t b0, b1;
-    GcTab::bases(threadIdx.x & 63, b0, b1);
-    const uint64_t n = a.G * a.N;
-    const uint64_t Npad = (uint64_t)a.nw * 64;
-    const uint64_t n_act = gc_active(a);
-    const uint32_t* msgs = reinterpret_cast<const uint32_t*>(a.gt_msgs);
-    uint32_t* vals = reinterpret_cast<uint32_t*>(a.sh_ev);
+    const T* msgs = reinterpret_cast<const T*>(a.gt_msgs);
+    T* vals = reinterpret_cast<T*>(a.sh_ev);
     constexpr int U = FHH_GT_EVAL_U;   // tests per lane per pass (U AES blocks in flight)
     const uint64_t stride = (uint64_t)gridDim.x * kGcThreads;
     for (uint64_t t0 = (uint64_t)blockIdx.x * kGcThreads + threadIdx.x; t0 < n_act; t0 += U * stride) {
@@ -744,49 +634,21 @@ __global__ __launch_bounds__(kGcThreads) void k_gt_eval_r32(GcArgs a) {
         for (int u = 0; u < U; u++) {
             const uint64_t t = tt[u];
             if (t >= n_act) continue;
-            vals[t] = row[u] ? (h[u][0] ^ msgs[(uint64_t)(row[u] - 1) * n + t]) : h[u][0];
+            vals[t] = row[u] ? (Sh::pad(h[u]) ^ msgs[(uint64_t)(row[u] - 1) * n + t]) : Sh::row0(h[u]);
         }
     }
 }
 
-// Per-child sums of the u32 node values [C][n] of the kernels above: workgroup (x, c) adds its slice of
-// child c's row, at most kRingSumSlice values, in u64 and adds the wave sums to sums[c] (zeroed by the
-// caller) with one atomic per wave. The u64 totals cannot wrap (n < 2^32 values below 2^32) and integer
-// addition commutes, so the host's single reduction mod 2^32 does not depend on the order of the adds.
+// Per-child sums of the u32 node values [C][n] of the Z_2^32 kernels above: workgroup (x, y) adds its slice of
+// child c = c0 + y's row, at most kRingSumSlice values, in u64 and adds the wave sums to dst[(g_off + c) pitch +
+// slot] (zeroed by the caller) with one atomic per wave; children past the level's C (ctl, the level loop) are
+// skipped. The u64 totals cannot wrap (n < 2^32 values below 2^32) and integer addition commutes, so the one
+// reduction mod 2^32 that follows does not depend on the order of the adds.
 constexpr int kRingSumThreads = 256;
 constexpr uint32_t kRingSumSlice = 4096;
-__global__ __launch_bounds__(kRingSumThreads) void k_ring32_child_sums(const uint32_t* vals, uint64_t n, uint64_t* sums) {
-    const uint64_t c = blockIdx.y;
-    const uint64_t lo = (uint64_t)blockIdx.x * kRingSumSlice;
-    const uint64_t hi = lo + kRingSumSlice < n ? lo + kRingSumSlice : n;
-    const uint32_t* row = vals + c * n;
-    uint64_t acc = 0;
-    for (uint64_t i = lo + threadIdx.x; i < hi; i += kRingSumThreads) acc += row[i];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off, 64);
-    if ((threadIdx.x & 63) == 0 && acc) atomicAdd(reinterpret_cast<unsigned long long*>(sums + c), (unsigned long long)acc);
-}
-
-hipError_t launch_ring32_child_sums(const uint32_t* vals, uint64_t n, uint64_t C, uint64_t* sums, hipStream_t stream) {
-    if (n == 0 || C == 0) return hipSuccess;
-    if (!vals || !sums) return hipErrorInvalidValue;
-    const uint64_t per = (n + kRingSumSlice - 1) / kRingSumSlice;
-    for (uint64_t c0 = 0; c0 < C; c0 += 65535) {   // grid.y holds 65535 children per launch
-        const uint64_t cc = C - c0 < 65535 ? C - c0 : 65535;
-        hipLaunchKernelGGL(k_ring32_child_sums, dim3((uint32_t)per, (uint32_t)cc), dim3(kRingSumThreads), 0, stream,
-                           vals + c0 * n, n, sums + c0);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
-    }
-    return hipSuccess;
-}
-
-// The level loop's form of the sums above (row-major Z_2^32 table, d = 2): child c of the chunk's G adds its
-// row's u64 total to partials[(g_off + c) * 4 + slot] (slot 0 the garbler's low sum, 2 the evaluator's: the
-// tile-major kernels' fused layout, which k_prune reads mod 2^32); children past the level's C (ctl) are skipped.
-__global__ __launch_bounds__(kRingSumThreads) void k_ring32_child_partials(const uint32_t* vals, uint64_t n, uint64_t c0,
-                                                                           const LoopCtl* ctl, uint64_t g_off,
-                                                                           uint64_t* partials, uint32_t slot) {
+__global__ __launch_bounds__(kRingSumThreads) void k_ring32_child_sums(const uint32_t* vals, uint64_t n, uint64_t c0,
+                                                                       const LoopCtl* ctl, uint64_t g_off, uint64_t* dst,
+                                                                       uint32_t pitch, uint32_t slot) {
     const uint64_t c = c0 + blockIdx.y;
     if (ctl && (ctl->abort || g_off + c >= ctl->C)) return;
     const uint64_t lo = (uint64_t)blockIdx.x * kRingSumSlice;
@@ -797,22 +659,35 @@ __global__ __launch_bounds__(kRingSumThreads) void k_ring32_child_partials(const
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off, 64);
     if ((threadIdx.x & 63) == 0 && acc)
-        atomicAdd(reinterpret_cast<unsigned long long*>(partials + (g_off + c) * 4 + slot), (unsigned long long)acc);
+        atomicAdd(reinterpret_cast<unsigned long long*>(dst + (g_off + c) * pitch + slot), (unsigned long long)acc);
 }
 
-hipError_t launch_ring32_child_partials(const uint32_t* vals, uint64_t n, uint64_t G, const LoopCtl* ctl, uint64_t g_off,
-                                        uint64_t* partials, uint32_t slot, hipStream_t stream) {
-    if (n == 0 || G == 0) return hipSuccess;
-    if (!vals || !partials) return hipErrorInvalidValue;
+static hipError_t ring32_sums(const uint32_t* vals, uint64_t n, uint64_t C, const LoopCtl* ctl, uint64_t g_off,
+                              uint64_t* dst, uint32_t pitch, uint32_t slot, hipStream_t stream) {
+    if (n == 0 || C == 0) return hipSuccess;
+    if (!vals || !dst) return hipErrorInvalidValue;
     const uint64_t per = (n + kRingSumSlice - 1) / kRingSumSlice;
-    for (uint64_t c0 = 0; c0 < G; c0 += 65535) {   // grid.y holds 65535 children per launch
-        const uint64_t cc = G - c0 < 65535 ? G - c0 : 65535;
-        hipLaunchKernelGGL(k_ring32_child_partials, dim3((uint32_t)per, (uint32_t)cc), dim3(kRingSumThreads), 0, stream,
-                           vals, n, c0, ctl, g_off, partials, slot);
+    for (uint64_t c0 = 0; c0 < C; c0 += 65535) {   // grid.y holds 65535 children per launch
+        const uint64_t cc = C - c0 < 65535 ? C - c0 : 65535;
+        hipLaunchKernelGGL(k_ring32_child_sums, dim3((uint32_t)per, (uint32_t)cc), dim3(kRingSumThreads), 0, stream,
+                           vals, n, c0, ctl, g_off, dst, pitch, slot);
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
     }
     return hipSuccess;
+}
+
+// child c's total to sums[c] (the party ABI's form 2)
+hipError_t launch_ring32_child_sums(const uint32_t* vals, uint64_t n, uint64_t C, uint64_t* sums, hipStream_t stream) {
+    return ring32_sums(vals, n, C, nullptr, 0, sums, 1, 0, stream);
+}
+
+// The level loop's form (row-major Z_2^32 table, d = 2): child c of the chunk's G adds its row's u64 total to
+// partials[(g_off + c) * 4 + slot] (slot 0 the garbler's low sum, 2 the evaluator's: the tile-major kernels'
+// fused layout, which k_prune reads mod 2^32)
+hipError_t launch_ring32_child_partials(const uint32_t* vals, uint64_t n, uint64_t G, const LoopCtl* ctl, uint64_t g_off,
+                                        uint64_t* partials, uint32_t slot, hipStream_t stream) {
+    return ring32_sums(vals, n, G, ctl, g_off, partials, 4, slot, stream);
 }
 
 // ---- r06: the garbled table on the labels OT's tile-major matrices ------------------------------
@@ -1415,32 +1290,41 @@ __global__ __launch_bounds__(kGcThreads) void k_gt_eval_tm(GcArgs a) {
     }
 }
 
-template <int B>
-static hipError_t gt_launch(const GcArgs& a, bool garble, hipStream_t stream) {
+// The launch grid of the kernels that fill the 128 KiB of tables once per workgroup and stride over their work:
+// `need` workgroups, at most per_cu for each CU of the current device, at least one
+static hipError_t gc_grid(uint64_t need, uint32_t per_cu, int* grid) {
     int dev = 0, cus = 0;
     hipError_t e = hipGetDevice(&dev);
     if (e != hipSuccess) return e;
     e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
     if (e != hipSuccess) return e;
-    const uint64_t n = a.G * a.N;
-    if constexpr (B <= kGtTmMaxBits) if (a.lab_tm) {   // r06: one wave per 512-test tile, one 160 KiB workgroup per CU
-        const uint64_t tiles = a.G * ((B > kGtTmPadBits ? a.nw + 7 : a.nw) / 8), need = (tiles + kGtWaves - 1) / kGtWaves;
-        const int grid = (int)(need < (uint64_t)cus ? (need ? need : 1) : (uint64_t)cus);
+    const uint64_t cap = (uint64_t)cus * per_cu;
+    *grid = (int)(need < cap ? (need ? need : 1) : cap);
+    return hipSuccess;
+}
+
+template <int B>
+static hipError_t gt_launch(const GcArgs& a, bool garble, hipStream_t stream) {
+    int grid = 0;
+    if (a.lab_tm) {   // r06: one wave per 512-test tile, one 160 KiB workgroup per CU
+        const uint64_t tiles = a.G * ((B > kGtTmPadBits ? a.nw + 7 : a.nw) / 8);
+        const hipError_t e = gc_grid((tiles + kGtWaves - 1) / kGtWaves, 1, &grid);
+        if (e != hipSuccess) return e;
         if (garble && a.ring32) hipLaunchKernelGGL((k_gt_garble_tm<B, true>), dim3(grid), dim3(kGcThreads), 0, stream, a);
         else if (garble) hipLaunchKernelGGL((k_gt_garble_tm<B, false>), dim3(grid), dim3(kGcThreads), 0, stream, a);
         else hipLaunchKernelGGL(k_gt_eval_tm<B>, dim3(grid), dim3(kGcThreads), 0, stream, a);
         return hipGetLastError();
     }
-    const uint64_t need = (n + kGcThreads - 1) / kGcThreads;
-    const int grid = (int)(need < (uint64_t)cus * 8 ? (need ? need : 1) : (uint64_t)cus * 8);
-    if constexpr (B > kGtTmPadBits) if (a.ring32) {   // Z_2^32 shares on the row-major labels (b = 3, 4)
-        if (garble) hipLaunchKernelGGL(k_gt_garble_r32<B>, dim3(grid), dim3(kGcThreads), 0, stream, a);
-        else hipLaunchKernelGGL(k_gt_eval_r32<B>, dim3(grid), dim3(kGcThreads), 0, stream, a);
+    if constexpr (B > kGtTmPadBits) {   // the row-major labels (b = 3, 4), shares in FE or Z_2^32
+        const hipError_t e = gc_grid((a.G * a.N + kGcThreads - 1) / kGcThreads, 8, &grid);
+        if (e != hipSuccess) return e;
+        if (garble && a.ring32) hipLaunchKernelGGL((k_gt_garble<B, true>), dim3(grid), dim3(kGcThreads), 0, stream, a);
+        else if (garble) hipLaunchKernelGGL((k_gt_garble<B, false>), dim3(grid), dim3(kGcThreads), 0, stream, a);
+        else if (a.ring32) hipLaunchKernelGGL((k_gt_eval<B, true>), dim3(grid), dim3(kGcThreads), 0, stream, a);
+        else hipLaunchKernelGGL((k_gt_eval<B, false>), dim3(grid), dim3(kGcThreads), 0, stream, a);
         return hipGetLastError();
     }
-    if (garble) hipLaunchKernelGGL(k_gt_garble<B>, dim3(grid), dim3(kGcThreads), 0, stream, a);
-    else hipLaunchKernelGGL(k_gt_eval<B>, dim3(grid), dim3(kGcThreads), 0, stream, a);
-    return hipGetLastError();
+    return hipErrorInvalidValue;   // no row-major table at b <= 2 (gt_dispatch)
 }
 
 static hipError_t gt_dispatch(const GcArgs& a, bool garble, hipStream_t stream) {
@@ -1450,8 +1334,9 @@ static hipError_t gt_dispatch(const GcArgs& a, bool garble, hipStream_t stream) 
     // tile-major labels: b <= 4; whole 512-test tiles per group at b <= 2 only (b = 3, 4: windows at any nw)
     if (a.lab_tm && (a.bits > (uint32_t)kGtTmMaxBits || (a.bits <= (uint32_t)kGtTmPadBits && a.nw % 8 != 0)))
         return hipErrorInvalidValue;
-    // Z_2^32: the tile-major kernels at b <= 4; b = 3, 4 also k_gt_garble_r32 / k_gt_eval_r32 on row-major labels
-    if (a.ring32 && !a.lab_tm && a.bits <= (uint32_t)kGtTmPadBits) return hipErrorInvalidValue;
+    // row-major labels: b = 3, 4 only, in FE and in Z_2^32 (k_gt_garble / k_gt_eval); gt_plan() makes every table
+    // at b <= 2 tile-major for all its callers (tests/host/gt_plan_host_test.cpp)
+    if (!a.lab_tm && a.bits <= (uint32_t)kGtTmPadBits) return hipErrorInvalidValue;
     switch (a.bits) {
         case 1: return gt_launch<1>(a, garble, stream);
         case 2: return gt_launch<2>(a, garble, stream);
@@ -1467,17 +1352,12 @@ hipError_t launch_gt_eval(const GcArgs& a, hipStream_t stream) { return gt_dispa
 
 template <int B>
 static hipError_t gc_launch(const GcArgs& a, bool garble, hipStream_t stream) {
-    int dev = 0, cus = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return e;
-    e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    if (e != hipSuccess) return e;
-    const uint64_t n = a.G * a.N;
-    const uint64_t need = (n + kGcThreads - 1) / kGcThreads;
     // 8 workgroups per CU (one resident per CU, each filling its tables once, measured -5.6 % for
     // evaluate at configs[1] but +3.2 % for evaluate and +0.7 % for the whole GC + OT crawl at 1M
     // clients, alternated twice; r03)
-    const int grid = (int)(need < (uint64_t)cus * 8 ? (need ? need : 1) : (uint64_t)cus * 8);
+    int grid = 0;
+    const hipError_t e = gc_grid((a.G * a.N + kGcThreads - 1) / kGcThreads, 8, &grid);
+    if (e != hipSuccess) return e;
     if (garble && a.ev_ot) hipLaunchKernelGGL(k_gc_garble_cot<B>, dim3(grid), dim3(kGcThreads), 0, stream, a);
     else if (garble) hipLaunchKernelGGL(k_gc_garble<B>, dim3(grid), dim3(kGcThreads), 0, stream, a);
     else if (a.ev_ot) hipLaunchKernelGGL((k_gc_eval<B, true>), dim3(grid), dim3(kGcThreads), 0, stream, a);

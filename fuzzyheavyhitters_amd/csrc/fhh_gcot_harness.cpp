@@ -311,7 +311,7 @@ static int gt_cot_host(fhh_ctx* ctx, uint64_t n, uint32_t bits, const uint8_t* g
     if (!(base_choice[0] & 1)) return ctx->fail(FHH_E_ARG, "gt_cot: s is the free-XOR Delta: its bit 0 must be 1");
     if (n > 0xFFFFFFFFull) return ctx->fail(FHH_E_ARG, "gt_cot: n must fit 32 bits");
     // the level loop's form of the table (gt_plan.h) at nw = ceil(n / 64); the row-major Z_2^32 kernels'
-    // (k_gt_garble_r32 / k_gt_eval_r32) node values are u32
+    // (k_gt_garble<b, true> / k_gt_eval<b, true>) node values are u32
     const GtPlan plan = ctx_gt_plan(ctx, GtCaller::kCotHost, bits, 1, 2, ring32, (n + 63) / 64);
     const bool tm = plan.tile_major;
     const bool val32 = plan.ring32 && !tm;

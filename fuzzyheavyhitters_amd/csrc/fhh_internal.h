@@ -235,10 +235,11 @@ struct GcArgs {
     uint64_t* sh_y;
     uint64_t* sh_ev;
     // r05d (FE levels, bits <= kGtMaxBits): the garbled table (oracle orc_gt_garble / orc_gt_eval):
-    // k_gt_garble writes rows 1 .. 2^bits - 1's messages SoA [2^bits - 1][G N] and the garbler's node
-    // values to sh_gb, k_gt_eval reads them and writes the evaluator's to sh_ev
+    // the garbler (k_gt_garble<B, RING> on row-major labels, bits = 3, 4; k_gt_garble_tm on tile-major ones)
+    // writes rows 1 .. 2^bits - 1's messages SoA [2^bits - 1][G N] and its node values to sh_gb, the evaluator
+    // (k_gt_eval<B, RING> / k_gt_eval_tm) reads them and writes its own to sh_ev
     uint64_t* gt_msgs;
-    // r06: 1 = ev_labels is the labels OT's tile-major matrix itself (Q for k_gt_garble, T for k_gt_eval;
+    // r06: 1 = ev_labels is the labels OT's tile-major matrix itself (Q for k_gt_garble_tm, T for k_gt_eval_tm;
     // fhh_ot.hip ot_tmaj) instead of one row-major label per OT (k_ot_rows_out). bits <= kGtTmPadBits needs
     // nw % 8 == 0 (the OT index (g bits + k) 64 nw + i puts a test's labels at one position of 512-OT tiles);
     // bits = 3, 4 take any nw (a bit's 512-test window starts at any even word of a tile)
@@ -250,7 +251,7 @@ struct GcArgs {
     uint64_t node_off;   // node_partials row of the launch's group 0 beyond g_off (the party ABI: its chunk's c_off)
     // r06 (lab_tm): 1 = the table's shares live in Z_2^32 instead of FE (row value lo32 of the
     // hash, pair (v, v +- 1 mod 2^32), 4-B messages [2^b - 1][n] u32; the partials' low sums taken mod 2^32).
-    // Without lab_tm (bits = 3, 4: k_gt_garble_r32 / k_gt_eval_r32) sh_gb / sh_ev hold u32 values [G N] too
+    // Without lab_tm (bits = 3, 4: k_gt_garble<B, true> / k_gt_eval<B, true>) sh_gb / sh_ev hold u32 values [G N] too
     uint32_t ring32;
 };
 // (kGtMaxBits, kGtTmMaxBits, kGtTmPadBits: gt_plan.h)

@@ -35,7 +35,7 @@ struct GtPlan {
     // stored values, no k_child_sums_fe pass)
     bool fused_sums;
     // Z_2^32 table shares in effect (requested, and this level runs the table): the tile-major table, or at
-    // b = 3, 4 on the row-major labels k_gt_garble_r32 / k_gt_eval_r32 with u32 node values
+    // b = 3, 4 on the row-major labels k_gt_garble<B, true> / k_gt_eval<B, true> with u32 node values
     bool ring32;
     uint64_t nw_gc, npad_gc;   // plane pitch in 64-client words; the OT index's clients per (child, bit)
     uint32_t per2;             // OTs per test of the share conversion (a FieldElm travels as a BlockPair)

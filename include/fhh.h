@@ -648,7 +648,7 @@ int fhh_gt_cot_host(fhh_ctx* ctx, uint64_t n, uint32_t bits, const uint8_t* gb_b
  * 1 .. 2^b - 1 send lo32(hash) ^ pair[o_r] (4 B); msgs / gb_share / ev_share as above, each value zero-extended
  * to u64 (gb - ev = eq mod 2^32). bits <= 4 on the tile-major kernels (bits = 3, 4 with nw = ceil(n / 64): the
  * OT index and the labels are those of the row-major form); with fhh_set_table_row_major, bits = 3, 4 on the
- * row-major k_gt_garble_r32 / k_gt_eval_r32 (u32 messages and node values on the device).
+ * row-major k_gt_garble<b, true> / k_gt_eval<b, true> (u32 messages and node values on the device).
  * Oracle: orc_gt_garble_ring32 / orc_gt_eval_ring32. */
 int fhh_gt_cot_ring32_host(fhh_ctx* ctx, uint64_t n, uint32_t bits, const uint8_t* gb_bits, const uint8_t* ev_bits,
                            uint32_t mask, uint64_t gate_base, const uint8_t base_seeds[128 * 2 * 16],
@@ -815,7 +815,7 @@ int fhh_variant_info(int variant, char* name, size_t cap, int* threads, int* gri
 int fhh_set_expand_grid(fhh_ctx* ctx, int blocks);
 /* Test / diagnostic ABI, not a product knob: on = 1 makes the level loop and fhh_gt_cot*_host run the garbled
  * tables of b = 3, 4 bits (d = 2) on the row-major labels: k_ot_rows_out's 16-B label per OT, k_gt_garble /
- * k_gt_eval (Z_2^32: k_gt_garble_r32 / k_gt_eval_r32) with stored node values and a separate sums pass.
+ * k_gt_eval (Z_2^32: their RING instantiations) with stored node values and a separate sums pass.
  * on = 0, the default, runs the tile-major kernels, which read the labels OT's Q / T themselves and add the
  * node values per child. Every output is the same either way; the row-major form is the A/B partner
  * (tools/gt_tm_ab.py). No effect at b <= 2. The party ABI (fhh_gb_* / fhh_ev_*) keeps the row-major labels at

@@ -9,7 +9,8 @@
 //          size no chunks)
 //   "-"    a combination the caller cannot form (form 1 carries no ring request; form 2 is refused at 2d > 4)
 // Pinned for the tests that set FHH_GC_CHUNK_BYTES from them: the d = 1 FieldElm estimate 402, the d = 2
-// tile-major 320; and that the party ABI at bits = 3, 4 is row-major and unfused whatever table_row_major says.
+// tile-major 320; that the party ABI at bits = 3, 4 is row-major and unfused whatever table_row_major says; and,
+// for every row, that no plan is a row-major table at bits <= kGtTmPadBits (those kernels exist at b = 3, 4 only).
 #include <cstdio>
 #include <cstring>
 #include <string>
@@ -124,6 +125,13 @@ int main() {
                                 flags_of(p, nw).c_str(), (unsigned long long)p.nw_gc, (unsigned long long)p.npad_gc, p.per2,
                                 (unsigned long long)p.bytes_per_test, e.flags, (unsigned long long)nw_gc, r.per2,
                                 (unsigned long long)e.est);
+                    return 1;
+                }
+                // the row-major table kernels exist at b = 3, 4 only (gt_dispatch refuses the rest)
+                if (p.table && !p.tile_major && r.bits <= (uint32_t)fhh::kGtTmPadBits) {
+                    std::printf("FAIL caller %d gc %u kind %u bits %u ring %d row_major %d nw %llu: a row-major table at "
+                                "b <= %d\n", (int)r.who, r.gc, r.kind, r.bits, c >> 1, c & 1, (unsigned long long)nw,
+                                fhh::kGtTmPadBits);
                     return 1;
                 }
                 checked++;

@@ -5,12 +5,13 @@ the code under test), for every kind of range, batch, level-block edge, source o
 shard cut, and the round trip export -> append -> crawl."""
 import ctypes
 import os
-import re
 import shutil
 import subprocess
 
 import numpy as np
 import pytest
+
+from kernel_usage import resource_usage
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CW_KERNEL = "_ZN3fhh17k_bincode_emit_cwEPK15HIP_vector_typeIjLj4EEPKmPhNS_8EmitArgsE"
@@ -85,26 +86,10 @@ def test_export_entry_points_refuse_null_ctx_and_bad_shapes(fhh):
     assert n.value == 77
 
 
-def test_emit_cw_kernel_does_not_spill(tmp_path):
+def test_emit_cw_kernel_does_not_spill():
     """k_bincode_emit_cw keeps a tile's 8 seed rows per lane in flight before the first LDS write; its LDS is the
     64 x 161-dword stage of the decoder."""
-    if not shutil.which("hipcc"):
-        pytest.skip("hipcc not available")
-    r = subprocess.run(["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "--cuda-device-only", "-c",
-                        "-Rpass-analysis=kernel-resource-usage",
-                        os.path.join(ROOT, "fuzzyheavyhitters_amd", "csrc", "fhh_bincode_out.hip"),
-                        "-o", str(tmp_path / "k.o")], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    usage, cur = {}, None
-    for line in r.stderr.splitlines():
-        m = re.search(r"remark: Function Name: (\S+)", line)
-        if m:
-            cur = m.group(1)
-            usage[cur] = {}
-            continue
-        m = re.search(r"remark:\s+([A-Za-z /\[\]]+?):\s+(\S+) \[", line)
-        if m and cur:
-            usage[cur][m.group(1).strip()] = m.group(2)
+    usage = resource_usage("fhh_bincode_out.hip")
     assert CW_KERNEL in usage, sorted(usage)
     k = usage[CW_KERNEL]
     assert k["ScratchSize [bytes/lane]"] == "0", k

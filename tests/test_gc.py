@@ -479,8 +479,10 @@ def test_gpu_crawl_with_ring32_table_equals_plain(gc_mode, ss_k):
 @pytest.mark.parametrize("n,bits", [(1, 2), (65, 1), (513, 1), (1000, 1), (1000, 2), (777, 3), (4097, 4),
                                     (GRID_STRIDE, 2)])
 def test_gpu_garbled_table_bit_exact(oracle, n, bits):
-    """fhh_gt_cot_host (labels OT + k_gt_garble + k_gt_eval) = the oracle chain bit for bit: zero and
-    active labels, every row's message, both parties' node values; gb - ev = eq mod p. The grid-stride
+    """fhh_gt_cot_host (labels OT + k_gt_garble_tm + k_gt_eval_tm: this caller's tables are tile-major at
+    every b <= 4; the row-major k_gt_garble<3|4, RING> / k_gt_eval<3|4, RING> run in test_table_tm_wide.py)
+    = the oracle chain bit for bit: zero and active labels, every row's message, both parties' node
+    values; gb - ev = eq mod p. The grid-stride
     case (more tiles than 16 per CU: the tile-major kernels' second pass through their loop, the last
     tile partial) runs one mask and counter setting, with the Python-int check on both ends' slices."""
     import fuzzyheavyhitters_amd as fhh

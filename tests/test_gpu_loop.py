@@ -74,7 +74,7 @@ GC_FORMS = [
     (2, "ot", False, False, 320),           # tile-major table on windows
     (2, "ot", True, False, 320),
     (2, "ot", False, True, 802),            # row-major table
-    (2, "ot", True, True, 802),             # ... in Z_2^32 (k_ring32_child_partials)
+    (2, "ot", True, True, 802),             # ... in Z_2^32 (k_ring32_child_sums into the partials)
     (3, "ot", False, False, 1202),          # no table at 2d = 6: the circuit with label shares
 ]
 

@@ -2,39 +2,13 @@
 (kDefaultVariant = 52 in csrc/fhh_host.cpp = X(52, PAIR, MW, NTL all true, ...) in
 csrc/fhh_kernels.hip, 1024 threads) must not spill and must keep 4 waves per SIMD.
 A spill once crept in through extra item-decode state and cost 4-8 %."""
-import os
-import re
-import shutil
-import subprocess
+from kernel_usage import resource_usage
 
-import pytest
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DEFAULT_EXPAND = "_ZN3fhh8k_expandILb1ELb1ELb1EEEvNS_12ExpandLaunchEPj"
 
 
-def _resource_usage(src, tmp_path):
-    r = subprocess.run(["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "--cuda-device-only", "-c",
-                        "-Rpass-analysis=kernel-resource-usage", os.path.join(ROOT, "fuzzyheavyhitters_amd", "csrc", src),
-                        "-o", str(tmp_path / "k.o")], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    usage, cur = {}, None
-    for line in r.stderr.splitlines():
-        m = re.search(r"remark: Function Name: (\S+)", line)
-        if m:
-            cur = m.group(1)
-            usage[cur] = {}
-            continue
-        m = re.search(r"remark:\s+([A-Za-z /\[\]]+?):\s+(\S+) \[", line)
-        if m and cur:
-            usage[cur][m.group(1).strip()] = m.group(2)
-    return usage
-
-
-def test_default_expand_variant_does_not_spill(tmp_path):
-    if not shutil.which("hipcc"):
-        pytest.skip("hipcc not available")
-    u = _resource_usage("fhh_kernels.hip", tmp_path)
+def test_default_expand_variant_does_not_spill():
+    u = resource_usage("fhh_kernels.hip")
     assert DEFAULT_EXPAND in u, "default k_expand instantiation not found (variant table changed?)"
     k = u[DEFAULT_EXPAND]
     assert k["ScratchSize [bytes/lane]"] == "0", k
@@ -48,12 +22,10 @@ def test_default_expand_variant_does_not_spill(tmp_path):
 OT_HASH_ROWS = tuple(f"_ZN3fhh19k_ot_{k}_hash_rowsILi{m}EEEvNS_6OtArgsE" for k in ("send", "recv") for m in range(4))
 
 
-def test_ot_hash_rows_do_not_spill(tmp_path):
+def test_ot_hash_rows_do_not_spill():
     """The transpose-fused OT hashes keep a lane's 32 tile words beside the AES; an unrolled
     round loop once spilled ~90 VGPRs. 160 KiB of LDS: tables + staging."""
-    if not shutil.which("hipcc"):
-        pytest.skip("hipcc not available")
-    u = _resource_usage("fhh_ot.hip", tmp_path)
+    u = resource_usage("fhh_ot.hip")
     for name in OT_HASH_ROWS:
         assert name in u, f"{name} not found"
         k = u[name]
@@ -62,27 +34,25 @@ def test_ot_hash_rows_do_not_spill(tmp_path):
         assert int(k["LDS Size [bytes/block]"]) == 163840, (name, k)
 
 
-def test_gc_and_ot_expand_kernels_do_not_spill(tmp_path):
+def test_gc_and_ot_expand_kernels_do_not_spill():
     """k_gc_garble / k_gc_eval at every share-string width b = 1..8, the garbled-table kernels and both
     OT expands (ChaCha12 since r06) stay in registers at >= 4 waves per SIMD."""
-    if not shutil.which("hipcc"):
-        pytest.skip("hipcc not available")
-    u = _resource_usage("fhh_gc.hip", tmp_path)
+    u = resource_usage("fhh_gc.hip")
     # both garblers (the ideal-OT one, the r05 one on the labels C-OT's zero labels with the garbler's
     # string folded in) and both evaluator forms
     names = [f"_ZN3fhh11k_gc_garbleILi{b}EEEvNS_6GcArgsE" for b in range(1, 9)]
     names += [f"_ZN3fhh15k_gc_garble_cotILi{b}EEEvNS_6GcArgsE" for b in range(1, 9)]
     names += [f"_ZN3fhh9k_gc_evalILi{b}ELb{f}EEEvNS_6GcArgsE" for b in range(1, 9) for f in (0, 1)]
-    # r05d: the FE levels' garbled table, b = 1..4
-    names += [f"_ZN3fhh11k_gt_garbleILi{b}EEEvNS_6GcArgsE" for b in range(1, 5)]
-    names += [f"_ZN3fhh9k_gt_evalILi{b}EEEvNS_6GcArgsE" for b in range(1, 5)]
+    # r05d: the garbled table on the row-major labels, b = 3, 4, shares in FE (0) and in Z_2^32 (1)
+    names += [f"_ZN3fhh11k_gt_garbleILi{b}ELb{r}EEEvNS_6GcArgsE" for b in (3, 4) for r in (0, 1)]
+    names += [f"_ZN3fhh9k_gt_evalILi{b}ELb{r}EEEvNS_6GcArgsE" for b in (3, 4) for r in (0, 1)]
+    # (b <= 2 is tile-major for every caller: no row-major kernel exists there, test_table_ring32_wide.py)
     # r06: the table kernels on the labels OT's tile-major Q / T (b <= 2)
     # (r06: FE and Z_2^32 shares as separate instantiations)
     names += [f"_ZN3fhh14k_gt_garble_tmILi{b}ELb{r}EEEvNS_6GcArgsE" for b in (1, 2) for r in (0, 1)
               if (b, r) != (2, 1)]
     names += [f"_ZN3fhh12k_gt_eval_tmILi{b}EEEvNS_6GcArgsE" for b in (1, 2)]
-    ot = _resource_usage("fhh_ot.hip", tmp_path)
-    u.update(ot)
+    u.update(resource_usage("fhh_ot.hip"))
     # r06: the ChaCha12 row-PRG expands (no LDS), and the labels OT's row transpose (mode 4, r05b)
     names += ["_ZN3fhh19k_ot_recv_expand_ccENS_6OtArgsE", "_ZN3fhh19k_ot_send_expand_ccENS_6OtArgsE",
               "_ZN3fhh13k_ot_rows_outENS_6OtArgsEi"]

@@ -1,5 +1,5 @@
 """Form 2 of the two-server GC + OT (fhh_gb_cfg.form = 2): the FE levels' garbled table with its shares in
-Z_2^32, at d = 1 (the tile-major kernels with the fused partials) and d = 2 (k_gt_garble_r32 / k_gt_eval_r32,
+Z_2^32, at d = 1 (the tile-major kernels with the fused partials) and d = 2 (k_gt_garble<4, true> / k_gt_eval<4, true>,
 u32 node values and k_ring32_child_sums).
 
 CPU: the leader's fhh_keep_values_ring32 against Python ints, the unchanged cfg layouts, two_party_crawl's
@@ -281,7 +281,7 @@ def test_gpu_form2_transcript_d1(oracle, ss_k, chunk, hold):
 @pytest.mark.parametrize("ss_k", [1, 2])
 @pytest.mark.parametrize("chunk", [0, 3], ids=["whole", "win3"])
 def test_gpu_form2_transcript_d2(oracle, ss_k, chunk):
-    """d = 2: the row-major labels, k_gt_garble_r32 / k_gt_eval_r32 (15 rows of u32 per test), u32 node values
+    """d = 2: the row-major labels, k_gt_garble<4, true> / k_gt_eval<4, true> (15 rows of u32 per test), u32 node values
     summed by k_ring32_child_sums; n = 201 (odd: rows 4-B aligned only), windows of 3 children."""
     shape, _ = _crawl_and_check(2, ss_k, chunk)
     assert [sum(w) for _, w in shape] == [4, 8, 12, 20, 20, 20, 20, 20]   # the plaintext crawl's children per level

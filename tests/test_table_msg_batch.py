@@ -5,17 +5,12 @@ What a hoisted load can get wrong is its predicate: row 0 has no message (its in
 dead tests of a tail tile index past the buffer. n = 513 and 1025 leave a tail tile with one live test and
 511 dead ones; n = 1 over several seeds reaches row 0 and rows 1..3; 511 / 512 are the tile's edges.
 Everything is compared with the oracle bit for bit: there is no tolerance."""
-import os
-import re
-import shutil
-import subprocess
-
 import numpy as np
 import pytest
 
 from test_gc import (FE_P, _cases, _colour_s, _oracle_table_chain, _oracle_table_chain_ring32, _pair, _sig)
+from kernel_usage import resource_usage
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 KEYS = ("ev_zero", "ev_active", "msgs", "gb_share", "ev_share")
 SHAPES = [(1, 2), (511, 2), (512, 2), (513, 2), (1025, 2), (513, 1)]
 
@@ -88,24 +83,10 @@ def test_gpu_crawl_513_clients_equals_plain(ring32):
     assert len(got.final) > 0 and max(plain.level_children) > 2
 
 
-def test_tile_major_table_kernels_fit_128_vgprs(tmp_path):
+def test_tile_major_table_kernels_fit_128_vgprs():
     """Every tile-major table kernel (b = 1..4, FE and Z_2^32 garblers, the evaluator) stays within 128 VGPRs
     with no spill and no scratch at 1024 threads: the batched loads must not cost the fourth wave per SIMD."""
-    if not shutil.which("hipcc"):
-        pytest.skip("hipcc not available")
-    r = subprocess.run(["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "--cuda-device-only", "-c",
-                        "-Rpass-analysis=kernel-resource-usage", os.path.join(ROOT, "fuzzyheavyhitters_amd", "csrc", "fhh_gc.hip"),
-                        "-o", str(tmp_path / "k.o")], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    usage, cur = {}, None
-    for line in r.stderr.splitlines():
-        m = re.search(r"remark: Function Name: (\S+)", line)
-        if m:
-            cur = usage.setdefault(m.group(1), {})
-            continue
-        m = re.search(r"remark:\s+([A-Za-z /\[\]]+?):\s+(\S+) \[", line)
-        if m and cur is not None:
-            cur[m.group(1).strip()] = m.group(2)
+    usage = resource_usage("fhh_gc.hip")
     names = [f"_ZN3fhh14k_gt_garble_tmILi{b}ELb{f}EEEvNS_6GcArgsE" for b in range(1, 5) for f in (0, 1)]
     names += [f"_ZN3fhh12k_gt_eval_tmILi{b}EEEvNS_6GcArgsE" for b in range(1, 5)]
     for name in names:

@@ -1,49 +1,25 @@
-"""The Z_2^32 garbled table at b = 3, 4 (the d = 2 tests): k_gt_garble_r32 / k_gt_eval_r32 on the row-major
-labels and the per-child sums kernel k_ring32_child_sums (csrc/fhh_gc.hip) — their register budgets (CPU,
+"""The Z_2^32 garbled table at b = 3, 4 (the d = 2 tests): k_gt_garble<3|4, true> / k_gt_eval<3|4, true> on the
+row-major labels and the per-child sums kernel k_ring32_child_sums (csrc/fhh_gc.hip) — their register budgets (CPU,
 hipcc cross-compile), the oracle's table at these widths, and the kernels bit for bit against the oracle chain
 through gc.table_cot(ring32=True) (fhh_gt_cot_ring32_host)."""
 import ctypes
 import itertools
-import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 import party_model_ring32 as pr
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _resource_usage(src, tmp_path):
-    r = subprocess.run(["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "--cuda-device-only", "-c",
-                        "-Rpass-analysis=kernel-resource-usage", os.path.join(ROOT, "fuzzyheavyhitters_amd", "csrc", src),
-                        "-o", str(tmp_path / "k.o")], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    usage, cur = {}, None
-    for line in r.stderr.splitlines():
-        m = re.search(r"remark: Function Name: (\S+)", line)
-        if m:
-            cur = m.group(1)
-            usage[cur] = {}
-            continue
-        m = re.search(r"remark:\s+([A-Za-z /\[\]]+?):\s+(\S+) \[", line)
-        if m and cur:
-            usage[cur][m.group(1).strip()] = m.group(2)
-    return usage
+from kernel_usage import resource_usage
 
 
-def test_ring32_table_kernels_do_not_spill(tmp_path):
-    """The new kernels by their own mangled names: no scratch, no spilled VGPR and >= 4 waves per SIMD at
-    1024 threads, like their FE siblings k_gt_garble<3, 4> / k_gt_eval<3, 4>; the sums kernel compiles for
-    gfx950 and needs neither scratch nor LDS."""
-    if not shutil.which("hipcc"):
-        pytest.skip("hipcc not available")
-    u = _resource_usage("fhh_gc.hip", tmp_path)
-    names = [f"_ZN3fhh15k_gt_garble_r32ILi{b}EEEvNS_6GcArgsE" for b in (3, 4)]
-    names += [f"_ZN3fhh13k_gt_eval_r32ILi{b}EEEvNS_6GcArgsE" for b in (3, 4)]
+def test_ring32_table_kernels_do_not_spill():
+    """The Z_2^32 instantiations by their own mangled names: no scratch, no spilled VGPR and >= 4 waves per SIMD
+    at 1024 threads, like their FE siblings k_gt_garble<3|4, false> / k_gt_eval<3|4, false>; the sums kernel
+    compiles for gfx950 and needs neither scratch nor LDS."""
+    u = resource_usage("fhh_gc.hip")
+    names = [f"_ZN3fhh11k_gt_garbleILi{b}ELb1EEEvNS_6GcArgsE" for b in (3, 4)]
+    names += [f"_ZN3fhh9k_gt_evalILi{b}ELb1EEEvNS_6GcArgsE" for b in (3, 4)]
     for name in names:
         assert name in u, f"{name} not found"
         k = u[name]
@@ -51,11 +27,11 @@ def test_ring32_table_kernels_do_not_spill(tmp_path):
         assert k["VGPRs Spill"] == "0", (name, k)
         assert int(k["Occupancy [waves/SIMD]"]) >= 4, (name, k)
         assert int(k["LDS Size [bytes/block]"]) == 131072, (name, k)   # the T-tables alone
-    sums = "_ZN3fhh19k_ring32_child_sumsEPKjmPm"
+    sums = "_ZN3fhh19k_ring32_child_sumsEPKjmmPKNS_7LoopCtlEmPmjj"
     assert sums in u, f"{sums} not found"
     assert u[sums]["ScratchSize [bytes/lane]"] == "0" and u[sums]["LDS Size [bytes/block]"] == "0", u[sums]
-    # only b = 3, 4 have row-major ring kernels (b <= 2 stays on the tile-major ones)
-    assert not any(re.search(r"k_gt_(garble|eval)_r32ILi[12]E", n) for n in u)
+    # only b = 3, 4 have row-major kernels, FE or ring (b <= 2 stays on the tile-major ones)
+    assert not any(re.search(r"k_gt_(garble|eval)ILi[12]E", n) for n in u)
 
 
 @pytest.mark.parametrize("bits", [3, 4])
@@ -94,7 +70,7 @@ def _grid_stride_n():
 @pytest.mark.gpu
 @pytest.mark.parametrize("n,bits", [(1, 4), (65, 3), (777, 3), (4097, 4), (GRID_STRIDE, 3)])
 def test_gpu_ring32_table_wide_bit_exact(oracle, n, bits):
-    """fhh_gt_cot_ring32_host at b = 3, 4 (labels OT + k_gt_garble_r32 + k_gt_eval_r32) = the oracle chain bit
+    """fhh_gt_cot_ring32_host at b = 3, 4 (labels OT + k_gt_garble<b, true> + k_gt_eval<b, true>) = the oracle chain bit
     for bit: zero and active labels, every 4-B message, both parties' values (zero-extended); gb - ev = eq mod
     2^32. Masks 0 and 1, ctr_off 0 and 256; the grid-stride case runs mask 1 at ctr_off 256 only."""
     import fuzzyheavyhitters_amd as fhh

@@ -6,7 +6,6 @@ self-test of the window addressing and the switch's ABI (CPU); on the GPU the si
 oracle and the level loop against the plain crawl."""
 import ctypes
 import os
-import re
 import shutil
 import subprocess
 
@@ -14,32 +13,17 @@ import numpy as np
 import pytest
 
 import test_gc as tg
+from kernel_usage import resource_usage
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FE_P = tg.FE_P
 
 
 # ---- CPU: register budget, the switch ------------------------------------------------------------------
-def test_wide_tile_major_table_kernels_fit_their_budget(tmp_path):
+def test_wide_tile_major_table_kernels_fit_their_budget():
     """1024 threads and 160 KiB of LDS (tables + the 2-KiB stages) leave 128 VGPRs per lane and no LDS on the
     CU: no scratch, no spilled VGPR, 4 waves per SIMD, for the FE and Z_2^32 garblers and the evaluator."""
-    if not shutil.which("hipcc"):
-        pytest.skip("hipcc not available")
-    r = subprocess.run(["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "--cuda-device-only", "-c",
-                        "-Rpass-analysis=kernel-resource-usage",
-                        os.path.join(ROOT, "fuzzyheavyhitters_amd", "csrc", "fhh_gc.hip"), "-o", str(tmp_path / "k.o")],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    usage, cur = {}, None
-    for line in r.stderr.splitlines():
-        m = re.search(r"remark: Function Name: (\S+)", line)
-        if m:
-            cur = m.group(1)
-            usage[cur] = {}
-            continue
-        m = re.search(r"remark:\s+([A-Za-z /\[\]]+?):\s+(\S+) \[", line)
-        if m and cur:
-            usage[cur][m.group(1).strip()] = m.group(2)
+    usage = resource_usage("fhh_gc.hip")
     names = [f"_ZN3fhh14k_gt_garble_tmILi{b}ELb{r}EEEvNS_6GcArgsE" for b in (3, 4) for r in (0, 1)]
     names += [f"_ZN3fhh12k_gt_eval_tmILi{b}EEEvNS_6GcArgsE" for b in (3, 4)]
     for name in names:
@@ -68,7 +52,8 @@ def test_gt_plan_host(tmp_path):
     """csrc/gt_plan.h on the host (tests/host/gt_plan_host_test.cpp): the form of the equality test for every
     caller, GC form, level kind, d = 1 .. 4, ring request, table_row_major and nw = 1 .. 16 384 against the literal
     table of what the level loop, gt_cot_host and party_begin decided before the header existed; the chunk-sizing
-    estimates 402 and 320 that the chunked loop tests use; the party ABI row-major and unfused at b = 3, 4."""
+    estimates 402 and 320 that the chunked loop tests use; the party ABI row-major and unfused at b = 3, 4; no
+    row-major table at b <= 2, where no row-major kernel exists."""
     if not shutil.which("hipcc"):
         pytest.skip("hipcc not available")
     exe = tmp_path / "gt_plan_host"
@@ -146,7 +131,7 @@ def test_gpu_wide_table_bit_exact(oracle, n, bits, row_major):
 @pytest.mark.parametrize("ss_k", [1, 2])
 def test_gpu_loop_d2_table_layouts_equal_plain(monkeypatch, ss_k, devices):
     """sim_crawl(gc="ot") at d = 2 with 3 000 clients (nw = 47, not a multiple of 8), FE and Z_2^32 table shares
-    (on the row-major labels: k_gt_garble_r32 / k_gt_eval_r32 + k_ring32_child_partials), whole levels and
+    (on the row-major labels: k_gt_garble<3|4, true> / k_gt_eval<3|4, true> + k_ring32_child_sums), whole levels and
     several chunks per level: every level's counts and the final (path, value) set equal the plain FE-mode
     crawl's, in both layouts."""
     import fuzzyheavyhitters_amd as fhh

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Same-process alternation of the d = 2 garbled table's two label layouts (fhh_set_table_row_major): the
-tile-major kernels k_gt_garble_tm<4> / k_gt_eval_tm<4> against k_ot_rows_out + the row-major kernels.
+tile-major kernels k_gt_garble_tm<4> / k_gt_eval_tm<4> against k_ot_rows_out + the row-major kernels
+k_gt_garble<4, RING> / k_gt_eval<4, RING> (RING: FE or Z_2^32 shares; Z_2^32 adds the k_ring32_child_sums pass).
     python tools/gt_tm_ab.py [--clients 1000000] [--threshold 0.001] [--rounds 3] [--runs loop|party,loop] [--out FILE]
 Workload: configs[3] (coords, d = 2 lat/lon, data_len 16), SoftSpoken k = 2. Runs: the drop-in two-server crawl
 in forms "table" and "table32" (both parties on one GPU, in-place channel, fresh CO15 material), and the
