@@ -88,29 +88,39 @@ __device__ __forceinline__ void key_schedule(const uint32_t key[4], uint32_t (&r
         for (int c = 0; c < 4; c++) rk[r][c] = w[4 * r + c];
 }
 
-using SkTab = TabT0R32<DevOpsX>;
-constexpr int kSketchThreads = 256;
+using SkTab = TabT0R32<DevOpsX>;    // k_sketch_fe255: T0 + rotations, the schedule in VGPRs
+using SkTab4 = Tab4T32<DevOpsX>;    // k_sketch_fe, k_sketch_fe_pc: four tables, one v_perm per lookup
+constexpr int kSketchThreads = 256;   // k_sketch_fe255
 
-// keystream block b (< 2^32): AES_seed(BE128(b)) -> two LE u64 draws (positions 2b, 2b+1)
-__device__ __forceinline__ void ks_block(uint64_t b, const uint32_t* tbl, uint32_t b0, uint32_t b1,
-                                         const uint32_t (&rk)[11][4], uint64_t& d0, uint64_t& d1) {
-    uint32_t s[1][4] = {{0u, 0u, __builtin_bswap32((uint32_t)(b >> 32)), __builtin_bswap32((uint32_t)b)}};
-    aes_rk<SkTab, 1>(s, tbl, b0, b1, rk);
-    d0 = (uint64_t)s[0][0] | ((uint64_t)s[0][1] << 32);
-    d1 = (uint64_t)s[0][2] | ((uint64_t)s[0][3] << 32);
+// the cipher input of keystream block b: the big-endian 128-bit counter (IV 0)
+__device__ __forceinline__ void ctr_block(uint64_t b, uint32_t (&st)[4]) {
+    st[0] = 0u;
+    st[1] = 0u;
+    st[2] = __builtin_bswap32((uint32_t)(b >> 32));
+    st[3] = __builtin_bswap32((uint32_t)b);
 }
 
-// the same with the schedule expanded on the fly (k_sketch_fe's default form)
+// key k's PrgStream key at `level`: its seed with bytes 12..15 ^= level (level 0 = the seed itself)
+__device__ __forceinline__ void load_seed(const uint8_t* seeds, uint64_t k, uint32_t level, uint32_t (&seed)[4]) {
+#pragma unroll
+    for (int c = 0; c < 4; c++) seed[c] = reinterpret_cast<const uint32_t*>(seeds)[4 * k + c];
+    seed[3] ^= level;
+}
+
+// keystream block b: AES_seed(BE128(b)) -> two LE u64 draws (positions 2b, 2b+1), the schedule
+// expanded on the fly (the sequential fallback's cipher)
 template <class Tab>
 __device__ __forceinline__ void ks_block_otf(uint64_t b, const uint32_t* tbl, uint32_t b0, uint32_t b1,
                                              const uint32_t (&key)[4], uint64_t& d0, uint64_t& d1) {
-    uint32_t s[1][4] = {{0u, 0u, __builtin_bswap32((uint32_t)(b >> 32)), __builtin_bswap32((uint32_t)b)}};
+    uint32_t s[1][4];
+    ctr_block(b, s[0]);
     aes_otf<Tab, 1>(s, tbl, b0, b1, key);
     d0 = (uint64_t)s[0][0] | ((uint64_t)s[0][1] << 32);
     d1 = (uint64_t)s[0][2] | ((uint64_t)s[0][3] << 32);
 }
 
-// draw `pos` of the key's stream (value v = low 62 bits): rand1..3 or node j = pos - 3
+// draw `pos` of the key's stream (value v = low 62 bits): rand1..3 or node j = pos - 3, every product
+// reduced (the r01 form of k_sketch_fe)
 __device__ __forceinline__ void sketch_draw(uint64_t pos, uint64_t v, uint64_t xv, uint64_t kxv, uint64_t F,
                                             int h, bool& rej, uint64_t& rnd0, uint64_t& rnd1, uint64_t& rx,
                                             uint64_t& r2x, uint64_t& rkx) {
@@ -166,8 +176,10 @@ __device__ __forceinline__ uint64_t fe_fold126(unsigned __int128 w) {
     return ((uint64_t)t & mask) + h2 + (h2 << 30);
 }
 
-// sketch_draw with the three inner-product terms accumulated unreduced, one fe_red128 per
-// accumulator per pass instead of a reduction per product.
+// draw `pos` of the key's stream (value v = low 62 bits): rand1..3 (segment lane 0 holds rand1,
+// rand2 = block 0; lane 1 holds rand3 = block 1, draw 0) or node j = pos - 3, with the three
+// inner-product terms accumulated unreduced, one fe_red128 per accumulator per pass instead of a
+// reduction per product.
 // CANON = false (the fused kernel, at most 4 draws per pass) multiplies the stored x / kx words as
 // they are (x = x' mod p gives the same sums mod p) and forms x r^2 as (x r) r: t = fold(x r) < 2^64
 // is added to <r, x> and multiplied by r for <r^2, x> — 12 instead of 15 32-bit partial products
@@ -200,12 +212,6 @@ __device__ __forceinline__ void sketch_draw_lazy(uint64_t pos, uint64_t v, uint6
         a2x += (unsigned __int128)t * v;                            // x r^2 (mod p)
     }
     akx += (unsigned __int128)kxv * v;
-}
-
-__device__ __forceinline__ uint64_t wave_fe_sum(uint64_t v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = fe_addc(v, __shfl_xor(v, off, 64));
-    return v;
 }
 
 // segment (LPK lanes = one key) reductions
@@ -255,19 +261,63 @@ __device__ __noinline__ void sketch_sequential_otf(const uint32_t* tbl, uint32_t
     o[5] = q3;
 }
 
+// The end of a key in k_sketch_fe and in k_sketch_fe_pc's consumers: the LPK lanes of segment `seg`
+// hold key k's partial sums, draws and rejection flags, and segment lane 0 of a live key stores
+// {<r,x>, <r^2,x>, <r,kx>, rand1, rand2, rand3} to outs[k]. After a from_rng redraw (P ~ 2^-32 per
+// draw) or under force_sequential that lane replays the key's sequential stream instead (the others
+// wait: correct, and rare outside the tests); only that path loads the seed and forms the row addresses.
+// The lane's state comes by reference, read in place once inlined: by value the compiler kept `rej`
+// as a lane mask in SGPRs across the consumer's phase loop and spilled 4-8 of them.
+template <int LPK, class Tab>
+__device__ __forceinline__ void sketch_key_end(const uint64_t& ax, const uint64_t& a2x, const uint64_t& akx,
+                                               const uint64_t& rnd0, const uint64_t& rnd1, const bool& rej,
+                                               bool kact, uint32_t seg, uint32_t sl, uint64_t k,
+                                               const SketchArgs& a, const uint64_t* xs, const uint64_t* kxs,
+                                               uint64_t F, uint64_t* outs, const uint32_t* tbl, uint32_t b0,
+                                               uint32_t b1) {
+    const uint64_t rej_mask = __ballot(rej);
+    const uint64_t seg_bits = (LPK == 64 ? ~0ull : ((1ull << LPK) - 1)) << (seg * LPK);
+    const bool key_rej = a.force_sequential || (rej_mask & seg_bits) != 0;
+    const uint64_t rx = seg_fe_sum<LPK>(ax), r2x = seg_fe_sum<LPK>(a2x), rkx = seg_fe_sum<LPK>(akx);
+    const uint64_t rand1 = __shfl(rnd0, seg * LPK, 64);
+    const uint64_t rand2 = __shfl(rnd1, seg * LPK, 64);
+    const uint64_t rand3 = __shfl(rnd0, seg * LPK + 1, 64);
+    if (kact && sl == 0) {
+        if (!key_rej) {
+            uint64_t* o = outs + 6 * k;
+            o[0] = rx;
+            o[1] = r2x;
+            o[2] = rkx;
+            o[3] = rand1;
+            o[4] = rand2;
+            o[5] = rand3;
+        } else {
+            uint32_t seed[4];
+            load_seed(a.seeds, k, a.level, seed);
+            sketch_sequential_otf<Tab>(tbl, b0, b1, seed, xs + k * F, kxs + k * F, F, outs + 6 * k);
+        }
+    }
+}
+
 // KPW keys per wave, LPK = 64 / KPW lanes per key: lane l of a key's segment produces keystream
-// blocks l, l + LPK, ... two per pass in lockstep, with the pass's (x, kx) loads issued first.
-// The key differs per segment, so the schedule is per lane: OTF = false keeps all 11 round keys
-// in VGPRs (r01: T0 + rotations, 256 threads, 157 VGPRs, 3 waves/SIMD); OTF = true expands it on
-// the fly per pass (4 extra lookups per round, shared by the pass's two blocks), which with the
-// four-table LDS layout (one v_perm per lookup) fits 1024 threads x <= 128 VGPRs.
-// SCHED 2: the schedule is computed once per key (every lane of the segment, through the tables)
-// and kept in LDS beside the tables (16 waves x KPW keys x 176 B = 22.5 KiB at KPW 8); a round
-// reads it with one broadcast ds_read_b128 instead of 4 lookups + the SubWord chain per pass.
-template <int KPW, class Tab = SkTab, int THR = kSketchThreads, int SCHED = 0, int NBP = 2>
-__global__ __launch_bounds__(THR) void k_sketch_fe(SketchArgs a) {
-    constexpr bool OTF = SCHED >= 1;   // lazy sums, out-of-line fallback, key expanded through Tab
-    constexpr int LPK = 64 / KPW;
+// blocks l, l + LPK, ... two per pass in lockstep, with the pass's (x, kx) loads issued first
+// (4 blocks per pass spills at 128 VGPRs: 0.88 vs 0.66 ms/level). The key differs per segment, so
+// its schedule is per lane, and SCHED says where it lives:
+//   2  the shipped form: computed once per key (every lane of the segment, through the tables) and kept
+//      in LDS beside the four-table layout (one v_perm per lookup; 16 waves x KPW keys x 176 B = 22.5 KiB
+//      at KPW 8); a round reads it with one broadcast ds_read_b128. 1024 threads x <= 128 VGPRs. 8 keys
+//      per wave is the main launch's form (at 256 nodes 130 blocks fill 9 passes of 16 slots, 90 %).
+//   1  expanded on the fly per pass (4 extra lookups per round, shared by the pass's two blocks);
+//      otherwise as 2. A/B only (fhh_sketch_set_impl 2).
+//   0  r01: all 11 round keys in VGPRs, T0 + rotations, 256 threads, 3 waves/SIMD, every product
+//      reduced. A/B only (fhh_sketch_set_impl 1).
+constexpr int kSketchNbp = 2;   // keystream blocks per lane per pass
+constexpr int sketch_fe_threads(int sched) { return sched == 0 ? kSketchThreads : 1024; }
+template <int KPW, int SCHED = 2>
+__global__ __launch_bounds__(sketch_fe_threads(SCHED)) void k_sketch_fe(SketchArgs a) {
+    using Tab = std::conditional_t<SCHED == 0, SkTab, SkTab4>;
+    constexpr bool OTF = SCHED >= 1;   // lazy sums, the one-block last pass
+    constexpr int LPK = 64 / KPW, THR = sketch_fe_threads(SCHED), NBP = kSketchNbp;
     __shared__ uint32_t tbl[Tab::kWords];
     __shared__ uint4 rks_lds[SCHED == 2 ? THR / 64 : 1][SCHED == 2 ? KPW : 1][11];
     for (int i = threadIdx.x; i < Tab::kWords; i += THR) tbl[i] = Tab::word(c_T0_sk.v, i);
@@ -292,20 +342,17 @@ __global__ __launch_bounds__(THR) void k_sketch_fe(SketchArgs a) {
         const uint64_t* const kxs = srv1 ? a.kx1 : a.kx;
         uint64_t* const outs = srv1 ? a.out1 : a.out;
         uint32_t seed[4];
-#pragma unroll
-        for (int c = 0; c < 4; c++) seed[c] = reinterpret_cast<const uint32_t*>(a.seeds)[4 * kk + c];
-        seed[3] ^= a.level;   // the level's stream (bytes 12..15; level 0 = the seed itself)
-        uint32_t rk[OTF ? 1 : 11][4];
-        if constexpr (!OTF) key_schedule(seed, rk, tbl, lane & 31);
-        const uint4* rkl = rks_lds[SCHED == 2 ? (threadIdx.x >> 6) : 0][SCHED == 2 ? seg : 0];
+        load_seed(a.seeds, kk, a.level, seed);
+        uint32_t rk[SCHED == 0 ? 11 : 1][4];
+        if constexpr (SCHED == 0) key_schedule(seed, rk, tbl, lane & 31);
+        uint4* const rkl = rks_lds[SCHED == 2 ? (threadIdx.x >> 6) : 0][SCHED == 2 ? seg : 0];   // the key's schedule
         if constexpr (SCHED == 2) {
             uint32_t full[11][4];
             key_schedule_tab<Tab>(seed, full, tbl, b0, b1);
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");   // the previous key's reads are done
             if (sl == 0) {
-                uint4* w = rks_lds[threadIdx.x >> 6][seg];
 #pragma unroll
-                for (int r = 0; r < 11; r++) w[r] = make_uint4(full[r][0], full[r][1], full[r][2], full[r][3]);
+                for (int r = 0; r < 11; r++) rkl[r] = make_uint4(full[r][0], full[r][1], full[r][2], full[r][3]);
             }
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
             __builtin_amdgcn_wave_barrier();
@@ -326,57 +373,45 @@ __global__ __launch_bounds__(THR) void k_sketch_fe(SketchArgs a) {
         const uint64_t* kx = kxs + kk * F;
         uint64_t rx = 0, r2x = 0, rkx = 0, rnd0 = 0, rnd1 = 0;
         bool rej = false;
-        // one pass: NB keystream blocks per lane (bb, bb + LPK, ...) and their draws' products
+        // one pass: NB keystream blocks per lane (bb, bb + LPK, ...) and their draws' products, the
+        // (x, kx) loads ahead of the AES; positions past the stream carry x = kx = 0 and are no-ops
         auto pass = [&](uint64_t bb, auto nbc) {
             constexpr int NB = decltype(nbc)::value;
-            // the pass's (x, kx) loads go ahead of the AES at 2 blocks per pass; at 4 their 32
-            // registers would be live across it, so they follow it (other waves hide the latency)
             uint64_t xv[2 * NB] = {}, kxv[2 * NB] = {};
-            auto load_xkx = [&]() {
 #pragma unroll
-                for (int q = 0; q < NB; q++)
+            for (int q = 0; q < NB; q++)
 #pragma unroll
-                    for (int h = 0; h < 2; h++) {
-                        const uint64_t pos = 2 * (bb + LPK * q) + h;
-                        if (pos >= 3 && pos < F + 3) {
-                            xv[2 * q + h] = x[pos - 3];
-                            kxv[2 * q + h] = kx[pos - 3];
-                        }
+                for (int h = 0; h < 2; h++) {
+                    const uint64_t pos = 2 * (bb + LPK * q) + h;
+                    if (pos >= 3 && pos < F + 3) {
+                        xv[2 * q + h] = x[pos - 3];
+                        kxv[2 * q + h] = kx[pos - 3];
                     }
-            };
-            if constexpr (NB <= 2) load_xkx();
+                }
             uint32_t st[NB][4];
 #pragma unroll
-            for (int q = 0; q < NB; q++) {
-                const uint64_t b = bb + LPK * q;
-                st[q][0] = 0u;
-                st[q][1] = 0u;
-                st[q][2] = __builtin_bswap32((uint32_t)(b >> 32));
-                st[q][3] = __builtin_bswap32((uint32_t)b);
-            }
+            for (int q = 0; q < NB; q++) ctr_block(bb + LPK * q, st[q]);
+            // the pass's counters differ only in byte 15 (the low byte of the big-endian
+            // block index) unless a lane's blocks straddle a multiple of 256: then rounds 1-2
+            // of the second block reuse the first's terms (aes_ctr_shared, 293 vs 320 lookups)
             if constexpr (SCHED == 2) {
-                // the pass's counters differ only in byte 15 (the low byte of the big-endian
-                // block index) unless a lane's blocks straddle a multiple of 256: then rounds 1-2
-                // of the second block reuse the first's terms (aes_ctr_shared, 293 vs 320 lookups)
                 const bool same_hi = (bb >> 8) == ((bb + LPK * (NB - 1)) >> 8);
                 if (pre_ok) aes_ctr_pre<Tab, NB, 3, 3>(st, tbl, b0, b1, RkLds{rkl}, pre);
                 else if (NB == 1 || __ballot(!same_hi) == 0) aes_lds_rk_ctr<Tab, NB, 3, 3>(st, tbl, b0, b1, rkl);
                 else aes_lds_rk<Tab, NB>(st, tbl, b0, b1, rkl);
-            } else if constexpr (OTF) aes_otf<Tab, NB>(st, tbl, b0, b1, seed);
+            } else if constexpr (SCHED == 1) aes_otf<Tab, NB>(st, tbl, b0, b1, seed);
             else aes_rk<Tab, NB>(st, tbl, b0, b1, rk);
-            if constexpr (NB > 2) load_xkx();
             unsigned __int128 ax = rx, a2x = r2x, akx = rkx;
 #pragma unroll
             for (int q = 0; q < NB; q++) {
                 const uint64_t b = bb + LPK * q;
-                if (!OTF && b >= nb) break;   // OTF: positions past the stream are no-ops
                 const uint64_t dr[2] = {(uint64_t)st[q][0] | ((uint64_t)st[q][1] << 32),
                                         (uint64_t)st[q][2] | ((uint64_t)st[q][3] << 32)};
 #pragma unroll
                 for (int h = 0; h < 2; h++) {
                     if constexpr (OTF)
-                        sketch_draw_lazy<(2 * NB > 4)>(2 * b + h, dr[h] & mask, xv[2 * q + h], kxv[2 * q + h], F, h,
-                                                       rej, rnd0, rnd1, ax, a2x, akx);
+                        sketch_draw_lazy<false>(2 * b + h, dr[h] & mask, xv[2 * q + h], kxv[2 * q + h], F, h, rej, rnd0,
+                                                rnd1, ax, a2x, akx);
                     else
                         sketch_draw(2 * b + h, dr[h] & mask, xv[2 * q + h], kxv[2 * q + h], F, h, rej, rnd0, rnd1,
                                     rx, r2x, rkx);
@@ -392,64 +427,12 @@ __global__ __launch_bounds__(THR) void k_sketch_fe(SketchArgs a) {
             for (uint64_t bb = sl; bb < nb; bb += NBP * LPK) {
                 // a pass whose blocks past the first are beyond the stream on every lane (the last
                 // pass of a 130-block key at LPK 8: blocks 128, 129) runs one block per lane: about
-                // half the AES and products of a full pass (OTF: past-the-stream positions are no-ops)
-                if (OTF && NBP > 1 && __ballot(bb + LPK < nb) == 0) pass(bb, std::integral_constant<int, 1>{});
+                // half the AES and products of a full pass
+                if (OTF && __ballot(bb + LPK < nb) == 0) pass(bb, std::integral_constant<int, 1>{});
                 else pass(bb, std::integral_constant<int, NBP>{});
             }
         }
-        // per-key rejection flag over the key's segment
-        const uint64_t rej_mask = __ballot(rej);
-        const uint64_t seg_bits = (LPK == 64 ? ~0ull : ((1ull << LPK) - 1)) << (seg * LPK);
-        const bool key_rej = a.force_sequential || (rej_mask & seg_bits) != 0;
-        rx = seg_fe_sum<LPK>(rx);
-        r2x = seg_fe_sum<LPK>(r2x);
-        rkx = seg_fe_sum<LPK>(rkx);
-        const uint64_t rand1 = __shfl(rnd0, seg * LPK, 64);
-        const uint64_t rand2 = __shfl(rnd1, seg * LPK, 64);
-        const uint64_t rand3 = __shfl(rnd0, seg * LPK + 1, 64);
-        if (kact && !key_rej && sl == 0) {
-            uint64_t* o = outs + 6 * k;
-            o[0] = rx;
-            o[1] = r2x;
-            o[2] = rkx;
-            o[3] = rand1;
-            o[4] = rand2;
-            o[5] = rand3;
-        } else if (kact && key_rej && sl == 0 && OTF) {
-            sketch_sequential_otf<Tab>(tbl, b0, b1, seed, x, kx, F, outs + 6 * k);
-        } else if (kact && key_rej && sl == 0) {
-            // sequential PrgStream with FE::from_rng redraws (field.rs:252-264) for this key
-            uint64_t pos = 0, cur_b = ~0ull, d[2] = {0, 0};
-            auto draw = [&]() -> uint64_t {
-                for (;;) {
-                    const uint64_t b = pos >> 1;
-                    if (b != cur_b) {
-                        if constexpr (!OTF) ks_block(b, tbl, b0, b1, rk, d[0], d[1]);
-                        cur_b = b;
-                    }
-                    const uint64_t v = d[pos & 1] & mask;
-                    pos++;
-                    if (v < kFeP_) return v;
-                }
-            };
-            const uint64_t q1 = draw(), q2 = draw(), q3 = draw();
-            uint64_t sx = 0, s2x = 0, skx = 0;
-            for (uint64_t j = 0; j < F; j++) {
-                const uint64_t r = draw();
-                const uint64_t r2 = fe_mulc(r, r);
-                const uint64_t xv = fe_canon_dev(x[j]), kxv = fe_canon_dev(kx[j]);
-                sx = fe_addc(sx, fe_mulc(xv, r));
-                s2x = fe_addc(s2x, fe_mulc(xv, r2));
-                skx = fe_addc(skx, fe_mulc(kxv, r));
-            }
-            uint64_t* o = outs + 6 * k;
-            o[0] = sx;
-            o[1] = s2x;
-            o[2] = skx;
-            o[3] = q1;
-            o[4] = q2;
-            o[5] = q3;
-        }
+        sketch_key_end<LPK, Tab>(rx, r2x, rkx, rnd0, rnd1, rej, kact, seg, sl, k, a, xs, kxs, F, outs, tbl, b0, b1);
     }
 }
 
@@ -478,7 +461,7 @@ constexpr int kPcBlocks = 3;
 template <int KPW, int PCB = kPcBlocks>
 __global__ __launch_bounds__(kPcThreads) void k_sketch_fe_pc(SketchArgs a) {
     constexpr int LPK = 64 / KPW;
-    using Tab = Tab4T32<DevOpsX>;
+    using Tab = SkTab4;
     __shared__ uint32_t tbl[Tab::kWords];
     __shared__ uint4 buf[kPcPairs][PCB][64];
     static_assert(sizeof(tbl) + sizeof(buf) <= 160 * 1024, "k_sketch_fe_pc: static LDS above the CU's 160 KiB");
@@ -517,19 +500,11 @@ __global__ __launch_bounds__(kPcThreads) void k_sketch_fe_pc(SketchArgs a) {
                 const uint64_t kk = k < a.n_keys ? k : task * KPW;
                 if (p == 0) {   // the task's key schedules, once per key, through the tables
                     uint32_t seed[4];
-#pragma unroll
-                    for (int c = 0; c < 4; c++) seed[c] = reinterpret_cast<const uint32_t*>(a.seeds)[4 * kk + c];
-                    seed[3] ^= a.level;   // the level's stream (bytes 12..15)
+                    load_seed(a.seeds, kk, a.level, seed);
                     key_schedule_tab<Tab>(seed, rk, tbl, b0, b1);
                 }
 #pragma unroll
-                for (int q = 0; q < PCB; q++) {
-                    const uint64_t b = (PCB * p + q) * LPK + sl;
-                    st[q][0] = 0u;
-                    st[q][1] = 0u;
-                    st[q][2] = __builtin_bswap32((uint32_t)(b >> 32));
-                    st[q][3] = __builtin_bswap32((uint32_t)b);
-                }
+                for (int q = 0; q < PCB; q++) ctr_block((PCB * p + q) * LPK + sl, st[q]);
                 {   // counters differing only in byte 15 (see k_sketch_fe): shared rounds 1-2
                     const uint64_t bf = PCB * p * LPK + sl, bl = (PCB * p + PCB - 1) * LPK + sl;
                     if (__ballot((bf >> 8) != (bl >> 8)) == 0) aes_rk_ctr<Tab, PCB, 3, 3>(st, tbl, b0, b1, rk);
@@ -573,8 +548,6 @@ __global__ __launch_bounds__(kPcThreads) void k_sketch_fe_pc(SketchArgs a) {
             const uint64_t step = g - 1;
             uint64_t p;
             const uint64_t task = task_of(step, p);
-            const uint64_t* xv = xv_n;
-            const uint64_t* kxv = kxv_n;
             if (task < ntasks) {   // wave-uniform
                 const uint64_t k = task * KPW + seg;
                 const bool kact = k < a.n_keys;
@@ -590,44 +563,18 @@ __global__ __launch_bounds__(kPcThreads) void k_sketch_fe_pc(SketchArgs a) {
                     const uint64_t dr[2] = {(uint64_t)s.x | ((uint64_t)s.y << 32), (uint64_t)s.z | ((uint64_t)s.w << 32)};
 #pragma unroll
                     for (int h = 0; h < 2; h++)   // positions past the stream carry x = kx = 0: no-ops
-                        sketch_draw_lazy<(2 * PCB > 4)>(2 * b + h, dr[h] & mask, xv[2 * q + h], kxv[2 * q + h], F, h,
-                                                        rej, rnd0, rnd1,
-                                         ax, a2x, akx);
+                        sketch_draw_lazy<(2 * PCB > 4)>(2 * b + h, dr[h] & mask, xv_n[2 * q + h], kxv_n[2 * q + h], F, h,
+                                                        rej, rnd0, rnd1, ax, a2x, akx);
                 }
                 ax = fe_red128(ax);
                 a2x = fe_red128(a2x);
                 akx = fe_red128(akx);
                 if (step + 1 < steps) load_xkx(step + 1);   // a phase ahead: they land during the barriers
-                if (p == passes - 1) {
-                    const uint64_t rej_mask = __ballot(rej);
-                    const uint64_t seg_bits = (LPK == 64 ? ~0ull : ((1ull << LPK) - 1)) << (seg * LPK);
-                    const bool key_rej = a.force_sequential || (rej_mask & seg_bits) != 0;
-                    const uint64_t rx = seg_fe_sum<LPK>((uint64_t)ax), r2x = seg_fe_sum<LPK>((uint64_t)a2x),
-                                   rkx = seg_fe_sum<LPK>((uint64_t)akx);
-                    const uint64_t rand1 = __shfl(rnd0, seg * LPK, 64);
-                    const uint64_t rand2 = __shfl(rnd1, seg * LPK, 64);
-                    const uint64_t rand3 = __shfl(rnd0, seg * LPK + 1, 64);
-                    if (kact && sl == 0) {
-                        if (!key_rej) {
-                            uint64_t* o = a.out + 6 * k;
-                            o[0] = rx;
-                            o[1] = r2x;
-                            o[2] = rkx;
-                            o[3] = rand1;
-                            o[4] = rand2;
-                            o[5] = rand3;
-                        } else {
-                            // a from_rng redraw (P ~ 2^-32 per draw) or force_sequential: this lane
-                            // replays the key's sequential stream; the workgroup's other waves wait
-                            // for it at the phase barrier (correct, and rare outside the tests)
-                            uint32_t seed[4];
-#pragma unroll
-                            for (int c = 0; c < 4; c++) seed[c] = reinterpret_cast<const uint32_t*>(a.seeds)[4 * k + c];
-                            seed[3] ^= a.level;
-                            sketch_sequential_otf<Tab>(tbl, b0, b1, seed, a.x + k * F, a.kx + k * F, F, a.out + 6 * k);
-                        }
-                    }
-                }
+                // (while a lane replays its key's sequential stream there, the workgroup's other waves
+                // wait for it at the phase barrier)
+                if (p == passes - 1)
+                    sketch_key_end<LPK, Tab>((uint64_t)ax, (uint64_t)a2x, (uint64_t)akx, rnd0, rnd1, rej, kact, seg, sl, k, a,
+                                        a.x, a.kx, F, a.out, tbl, b0, b1);
             }
         }
         __syncthreads();   // the producers may overwrite the buffer
@@ -635,42 +582,46 @@ __global__ __launch_bounds__(kPcThreads) void k_sketch_fe_pc(SketchArgs a) {
     }
 }
 
-constexpr int kSketchKeysPerWave = 4;
-// default form: 8 keys per wave (8 lanes per key: at 256 nodes 130 blocks fill 9 passes of 16
-// slots, 90 % of the slots), four-table LDS layout, 1024 threads, round keys in LDS
-constexpr int kSketchKpwOtf = 8;
-constexpr int kSketchThreadsOtf = 1024;
-constexpr int kSketchNbpOtf = 2;   // 4 blocks per pass (16 keys per wave) spills at 128 VGPRs: 0.88 vs 0.66 ms/level
-using SkTab4 = Tab4T32<DevOpsX>;
+// CU count of the current device, queried once per device (the sketch launches run per level; the
+// shard threads of a multi-device ctx may fill the cache concurrently, hence the atomics)
+static int sketch_cus() {
+    static std::atomic<int> cache[64] = {};
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
+    int cus = cache[dev].load(std::memory_order_relaxed);
+    if (!cus) {
+        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
+        cache[dev].store(cus, std::memory_order_relaxed);
+    }
+    return cus;
+}
 
+// workgroups of `kern` at `thr` threads that the current device holds at once: a grid-stride sketch
+// kernel is launched with at most this many, its keys strided over the one resident wave set
 template <class K>
-static hipError_t launch_sketch_kernel(K kern, int thr, int kpw, const SketchArgs& a, hipStream_t stream) {
-    int cus = 256, dev = 0, per_cu = 0;
-    (void)hipGetDevice(&dev);
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+static uint64_t sketch_resident_blocks(K kern, int thr) {
+    int per_cu = 0;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(kern), thr, 0) !=
             hipSuccess || per_cu < 1)
         per_cu = 1;
-    const uint64_t wpb = thr / 64;
-    const uint64_t waves_needed = (a.n_keys + kpw - 1) / kpw;
-    uint64_t blocks = (waves_needed + wpb - 1) / wpb;
-    const uint64_t cap = (uint64_t)cus * per_cu;   // one resident wave set; keys are strided over it
-    if (blocks > cap) blocks = cap;
-    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(thr), 0, stream, a);
-    return hipGetLastError();
+    return (uint64_t)sketch_cus() * per_cu;
 }
 
-// The default form with the key-to-wave granularity chosen per launch. Keys are strided over one
+// The fused form with the key-to-wave granularity chosen per launch. Keys are strided over one
 // resident wave set (W = CUs x 16 waves), a task = KPW keys of LPK = 64 / KPW lanes each, so a
 // launch takes ceil(tasks / W) rounds of ceil(ceil(nb / LPK) / NBP) passes. At configs[4] (100k
 // keys, 256 nodes, nb = 130) LPK 8 alone needs 3.05 rounds: the fourth runs 212 of 4096 waves for
 // as long as a full round (the kernel is latency-bound, a lone wave is not faster), 36 passes where
 // 24.8 would do. plan_sketch splits such a launch: R full LPK-8 rounds, then the remaining keys in
 // one launch with the LPK that needs the fewest passes (LPK 64: 1 round of 2 passes), 29 in all.
-template <int KPW>
+template <int KPW, int SCHED = 2>
 static hipError_t launch_sketch_lds(const SketchArgs& a, hipStream_t stream) {
-    return launch_sketch_kernel(k_sketch_fe<KPW, SkTab4, kSketchThreadsOtf, 2, kSketchNbpOtf>, kSketchThreadsOtf, KPW,
-                                a, stream);
+    constexpr int thr = sketch_fe_threads(SCHED);
+    const uint64_t wpb = thr / 64;
+    const uint64_t waves_needed = (a.n_keys + KPW - 1) / KPW;
+    const uint64_t blocks = std::min((waves_needed + wpb - 1) / wpb, sketch_resident_blocks(k_sketch_fe<KPW, SCHED>, thr));
+    hipLaunchKernelGGL((k_sketch_fe<KPW, SCHED>), dim3((unsigned)blocks), dim3(thr), 0, stream, a);
+    return hipGetLastError();
 }
 
 static hipError_t launch_sketch_lpk(int lpk, const SketchArgs& a, hipStream_t stream) {
@@ -683,20 +634,14 @@ static hipError_t launch_sketch_lpk(int lpk, const SketchArgs& a, hipStream_t st
     }
 }
 
-// resident waves of the LDS-schedule kernel on the current device (cached per device)
+// resident waves of the fused kernel on the current device (cached per device)
 static uint64_t sketch_resident_waves() {
     static std::atomic<uint64_t> cache[64] = {};
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
     uint64_t w = cache[dev].load(std::memory_order_relaxed);
     if (!w) {
-        int cus = 256, per_cu = 0;
-        (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(
-                &per_cu, reinterpret_cast<const void*>(k_sketch_fe<8, SkTab4, kSketchThreadsOtf, 2, kSketchNbpOtf>),
-                kSketchThreadsOtf, 0) != hipSuccess || per_cu < 1)
-            per_cu = 1;
-        w = (uint64_t)(cus > 0 ? cus : 256) * per_cu * (kSketchThreadsOtf / 64);
+        w = sketch_resident_blocks(k_sketch_fe<8>, sketch_fe_threads(2)) * (sketch_fe_threads(2) / 64);
         cache[dev].store(w, std::memory_order_relaxed);
     }
     return w;
@@ -704,7 +649,7 @@ static uint64_t sketch_resident_waves() {
 
 // cost in passes of one launch of n keys at LPK lanes per key (+ half a pass per round for the key
 // schedule, the reductions and the stores)
-static double sketch_launch_cost(uint64_t n, uint64_t nb, int lpk, uint64_t W, int nbp = kSketchNbpOtf) {
+static double sketch_launch_cost(uint64_t n, uint64_t nb, int lpk, uint64_t W, int nbp) {
     if (n == 0) return 0.0;
     const uint64_t kpw = 64 / lpk, tasks = (n + kpw - 1) / kpw, rounds = (tasks + W - 1) / W;
     const uint64_t passes = ((nb + lpk - 1) / lpk + nbp - 1) / nbp;
@@ -713,12 +658,7 @@ static double sketch_launch_cost(uint64_t n, uint64_t nb, int lpk, uint64_t W, i
 
 // W = resident waves (fused form, nbp = 2 blocks per lane per pass) or resident producer / consumer
 // pairs (nbp = kPcBlocks = 3 blocks per producer lane per phase)
-SketchPlan plan_sketch_nbp(uint64_t n_keys, uint32_t n_nodes, uint64_t W, int nbp);
-SketchPlan plan_sketch(uint64_t n_keys, uint32_t n_nodes, uint64_t W) {
-    return plan_sketch_nbp(n_keys, n_nodes, W, kSketchNbpOtf);
-}
-
-SketchPlan plan_sketch_nbp(uint64_t n_keys, uint32_t n_nodes, uint64_t W, int nbp) {
+static SketchPlan plan_sketch_nbp(uint64_t n_keys, uint32_t n_nodes, uint64_t W, int nbp) {
     static const int kLpk[4] = {8, 16, 32, 64};
     const uint64_t nb = ((uint64_t)n_nodes + 4) / 2;
     SketchPlan best{n_keys, 8, 8};
@@ -740,6 +680,10 @@ SketchPlan plan_sketch_nbp(uint64_t n_keys, uint32_t n_nodes, uint64_t W, int nb
     return best;
 }
 
+SketchPlan plan_sketch(uint64_t n_keys, uint32_t n_nodes, uint64_t W) {
+    return plan_sketch_nbp(n_keys, n_nodes, W, kSketchNbp);
+}
+
 extern "C" int fhh_sketch_plan(uint64_t n_keys, uint32_t n_nodes, uint64_t resident_waves, uint64_t* n_main,
                                int* lpk_main, int* lpk_tail) {
     if (!n_main || !lpk_main || !lpk_tail || resident_waves == 0) return FHH_E_ARG;
@@ -752,7 +696,8 @@ extern "C" int fhh_sketch_plan(uint64_t n_keys, uint32_t n_nodes, uint64_t resid
 
 // impl (fhh_sketch_set_impl): 0 = default (schedule once per key in LDS, 1024 threads, planned
 // key granularity), 1 = the r01 kernel, 2 = the schedule expanded on the fly per pass, 3 = the
-// default kernel at LPK 8 for every key (the form before plan_sketch)
+// default kernel at LPK 8 for every key (the form before plan_sketch), 4 = the producer / consumer
+// kernel for every key
 static int g_sketch_impl = 0;
 extern "C" int fhh_sketch_set_impl(int impl) {
     if (impl < 0 || impl > 4) return FHH_E_ARG;
@@ -781,34 +726,26 @@ static hipError_t launch_sketch_pc_lpk(int lpk, const SketchArgs& a, int cus, hi
     }
 }
 
-// CU count of the current device, queried once per device (the sketch launches run per level; the
-// shard threads of a multi-device ctx may fill the cache concurrently, hence the atomics)
-static int sketch_cus() {
-    static std::atomic<int> cache[64] = {};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
-    int cus = cache[dev].load(std::memory_order_relaxed);
-    if (!cus) {
-        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
-        cache[dev].store(cus, std::memory_order_relaxed);
-    }
-    return cus;
+// keys [off, off + n) of server `srv` of a batch (0, or 1 of a two-server batch) as a one-server launch
+static SketchArgs sketch_slice(const SketchArgs& a, int srv, uint64_t off, uint64_t n) {
+    const uint64_t* xs = srv ? a.x1 : a.x;
+    const uint64_t* kxs = srv ? a.kx1 : a.kx;
+    SketchArgs t = a;
+    t.n_srv = 0;
+    t.seeds = a.seeds + 16 * off;
+    t.x = xs ? xs + off * a.n_nodes : nullptr;
+    t.kx = kxs ? kxs + off * a.n_nodes : nullptr;
+    t.out = (srv ? a.out1 : a.out) + 6 * off;
+    t.n_keys = n;
+    return t;
 }
 
-static hipError_t launch_sketch_pc(const SketchArgs& a, hipStream_t stream) {
+static hipError_t launch_sketch_pc(const SketchArgs& a, hipStream_t stream) {   // one server's keys
     const int cus = sketch_cus();
     const SketchPlan p = plan_sketch_nbp(a.n_keys, a.n_nodes, (uint64_t)cus * kPcPairs, kPcBlocks);
-    SketchArgs m = a;
-    m.n_keys = p.n_main;
-    hipError_t e = launch_sketch_pc_lpk(p.lpk_main, m, cus, stream);
+    const hipError_t e = launch_sketch_pc_lpk(p.lpk_main, sketch_slice(a, 0, 0, p.n_main), cus, stream);
     if (e != hipSuccess || p.n_main == a.n_keys) return e;
-    SketchArgs t = a;
-    t.seeds = a.seeds + 16 * p.n_main;
-    t.x = a.x ? a.x + p.n_main * a.n_nodes : nullptr;
-    t.kx = a.kx ? a.kx + p.n_main * a.n_nodes : nullptr;
-    t.out = a.out + 6 * p.n_main;
-    t.n_keys = a.n_keys - p.n_main;
-    return launch_sketch_pc_lpk(p.lpk_tail, t, cus, stream);
+    return launch_sketch_pc_lpk(p.lpk_tail, sketch_slice(a, 0, p.n_main, a.n_keys - p.n_main), cus, stream);
 }
 
 hipError_t launch_sketch_fe(const SketchArgs& a, hipStream_t stream) { return launch_sketch_fe2(a, stream, stream); }
@@ -817,27 +754,16 @@ hipError_t launch_sketch_fe(const SketchArgs& a, hipStream_t stream) { return la
 // on `tail_stream`: a caller with a second stream lets the tail fill the main launch's ragged end
 hipError_t launch_sketch_fe2(const SketchArgs& a, hipStream_t stream, hipStream_t tail_stream) {
     if (a.n_keys == 0) return hipSuccess;
-    if (g_sketch_impl == 4 && a.n_srv) {   // the producer / consumer kernel takes one server at a time
-        for (int srv = 0; srv < 2; srv++) {
-            SketchArgs o = a;
-            o.n_srv = 0;
-            o.n_keys = srv ? a.n_keys - a.n_srv : a.n_srv;
-            if (srv) {
-                o.x = a.x1;
-                o.kx = a.kx1;
-                o.out = a.out1;
-            }
-            const hipError_t e = launch_sketch_pc(o, stream);
+    const uint64_t ns = a.n_srv ? a.n_srv : a.n_keys;   // server 0's keys
+    if (g_sketch_impl == 4) {   // the producer / consumer kernel takes one server at a time
+        for (int srv = 0; srv < (a.n_srv ? 2 : 1); srv++) {
+            const hipError_t e = launch_sketch_pc(sketch_slice(a, srv, 0, srv ? a.n_keys - ns : ns), stream);
             if (e != hipSuccess) return e;
         }
         return hipSuccess;
     }
-    if (g_sketch_impl == 4) return launch_sketch_pc(a, stream);
-    if (g_sketch_impl == 1)
-        return launch_sketch_kernel(k_sketch_fe<kSketchKeysPerWave>, kSketchThreads, kSketchKeysPerWave, a, stream);
-    if (g_sketch_impl == 2)
-        return launch_sketch_kernel(k_sketch_fe<kSketchKpwOtf, SkTab4, kSketchThreadsOtf, 1, kSketchNbpOtf>,
-                                    kSketchThreadsOtf, kSketchKpwOtf, a, stream);
+    if (g_sketch_impl == 1) return launch_sketch_lds<4, 0>(a, stream);   // r01: 4 keys per wave
+    if (g_sketch_impl == 2) return launch_sketch_lds<8, 1>(a, stream);
     if (g_sketch_impl == 3) return launch_sketch_lpk(8, a, stream);
     const SketchPlan p = plan_sketch(a.n_keys, a.n_nodes, sketch_resident_waves());
     SketchArgs m = a;
@@ -847,21 +773,11 @@ hipError_t launch_sketch_fe2(const SketchArgs& a, hipStream_t stream, hipStream_
     // the tail: the keys past n_main, in one round of the producer / consumer form (r03, configs[4]: its
     // 3 blocks per lane cover a 130-block key at LPK 64 in one pass where the fused form takes two: 16.2
     // vs 28.8 us; the main launch stays fused, 227 vs 236 us); one launch per server the tail touches
-    const uint64_t ns = a.n_srv ? a.n_srv : a.n_keys;
     for (int srv = 0; srv < (a.n_srv ? 2 : 1); srv++) {
         const uint64_t lo = std::max<uint64_t>(p.n_main, srv * ns), hi = srv ? a.n_keys : std::min(a.n_keys, ns);
         if (lo >= hi) continue;
-        const uint64_t off = lo - srv * ns;   // the server's first tail key
-        SketchArgs t = a;
-        t.n_srv = 0;
-        t.seeds = a.seeds + 16 * off;
-        const uint64_t* xs = srv ? a.x1 : a.x;
-        const uint64_t* kxs = srv ? a.kx1 : a.kx;
-        t.x = xs ? xs + off * a.n_nodes : nullptr;
-        t.kx = kxs ? kxs + off * a.n_nodes : nullptr;
-        t.out = (srv ? a.out1 : a.out) + 6 * off;
-        t.n_keys = hi - lo;
-        e = launch_sketch_pc_lpk(p.lpk_tail, t, sketch_cus(), tail_stream);
+        // (lo - srv * ns: the server's first tail key)
+        e = launch_sketch_pc_lpk(p.lpk_tail, sketch_slice(a, srv, lo - srv * ns, hi - lo), sketch_cus(), tail_stream);
         if (e != hipSuccess) return e;
     }
     return hipSuccess;
@@ -1034,13 +950,7 @@ __device__ __forceinline__ void fe255_draw_blocks(uint64_t m, const uint32_t* tb
                                                   const uint32_t (&rk)[11][4], uint32_t (&d)[8]) {
     uint32_t st[2][4];
 #pragma unroll
-    for (int h = 0; h < 2; h++) {
-        const uint64_t b = 2 * m + h;
-        st[h][0] = 0u;
-        st[h][1] = 0u;
-        st[h][2] = __builtin_bswap32((uint32_t)(b >> 32));
-        st[h][3] = __builtin_bswap32((uint32_t)b);
-    }
+    for (int h = 0; h < 2; h++) ctr_block(2 * m + h, st[h]);
     aes_rk<SkTab, 2>(st, tbl, b0, b1, rk);
 #pragma unroll
     for (int k = 0; k < 4; k++) {
@@ -1068,9 +978,7 @@ __global__ __launch_bounds__(kSketchThreads) void k_sketch_fe255(Sketch255Args a
         const bool kact = k < a.n_keys;
         const uint64_t kk = kact ? k : kbase;
         uint32_t seed[4];
-#pragma unroll
-        for (int c = 0; c < 4; c++) seed[c] = reinterpret_cast<const uint32_t*>(a.seeds)[4 * kk + c];
-        seed[3] ^= a.level;
+        load_seed(a.seeds, kk, a.level, seed);
         uint32_t rk[11][4];
         key_schedule(seed, rk, tbl, lane & 31);
         const uint32_t* x = a.x + kk * F * 8;
@@ -1166,16 +1074,9 @@ constexpr int kSketch255KeysPerWave = 4;   // 16 lanes per key
 
 hipError_t launch_sketch_fe255(const Sketch255Args& a, hipStream_t stream) {
     if (a.n_keys == 0) return hipSuccess;
-    int cus = 256, dev = 0, per_cu = 0;
-    (void)hipGetDevice(&dev);
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    const void* fn = reinterpret_cast<const void*>(&k_sketch_fe255<kSketch255KeysPerWave>);
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, kSketchThreads, 0) != hipSuccess || per_cu < 1)
-        per_cu = 1;
     const uint64_t waves_needed = (a.n_keys + kSketch255KeysPerWave - 1) / kSketch255KeysPerWave;
-    uint64_t blocks = (waves_needed + 3) / 4;
-    const uint64_t cap = (uint64_t)cus * per_cu;
-    if (blocks > cap) blocks = cap;
+    const uint64_t blocks = std::min((waves_needed + 3) / 4,
+                                     sketch_resident_blocks(k_sketch_fe255<kSketch255KeysPerWave>, kSketchThreads));
     hipLaunchKernelGGL(k_sketch_fe255<kSketch255KeysPerWave>, dim3((unsigned)blocks), dim3(kSketchThreads), 0, stream,
                        a);
     return hipGetLastError();

@@ -34,6 +34,30 @@ def test_ot_hash_rows_do_not_spill():
         assert int(k["LDS Size [bytes/block]"]) == 163840, (name, k)
 
 
+def test_fe_sketch_kernels_resources():
+    """The shipped FE sketch kernels (fhh_sketch.hip): the fused k_sketch_fe<KPW, SCHED = 2> and the producer /
+    consumer k_sketch_fe_pc<KPW, 3> at KPW = 1, 2, 4, 8 keys per wave. 1024 threads at 4 waves per SIMD leave
+    128 VGPRs; the only scratch is the out-of-line sequential fallback's frame. LDS: 128 KiB of tables + the
+    fused kernel's per-key round keys (16 waves x KPW keys x 11 x 16 B) or the producer / consumer hand-over
+    buffer (8 pairs x 3 blocks x 64 lanes x 16 B). Beside them k_sketch_fe may be built only in the two forms
+    that the suite's r01-256 / otf-1024 cases run, <4, 0> (r01) and <8, 1> (on the fly), and in no other."""
+    u = resource_usage("fhh_sketch.hip")
+    lds = {f"_ZN3fhh11k_sketch_feILi{kpw}ELi2EEEvNS_10SketchArgsE": 131072 + 16 * kpw * 176 for kpw in (1, 2, 4, 8)}
+    assert sorted(lds.values()) == [133888, 136704, 142336, 153600]
+    lds.update({f"_ZN3fhh14k_sketch_fe_pcILi{kpw}ELi3EEEvNS_10SketchArgsE": 131072 + 24576 for kpw in (1, 2, 4, 8)})
+    for name, want in lds.items():
+        assert name in u, f"{name} not found"
+        k = u[name]
+        assert k["VGPRs Spill"] == "0", (name, k)
+        assert int(k["ScratchSize [bytes/lane]"]) <= 32, (name, k)
+        assert int(k["Occupancy [waves/SIMD]"]) >= 4, (name, k)
+        assert int(k["LDS Size [bytes/block]"]) == want, (name, k)
+    # (k_sketch_fe255 and k_sketch_fe_pc mangle to other prefixes: 14k_sketch_fe...)
+    others = {n for n in u if n.startswith("_ZN3fhh11k_sketch_feI") and n not in lds}
+    assert others <= {"_ZN3fhh11k_sketch_feILi4ELi0EEEvNS_10SketchArgsE",
+                      "_ZN3fhh11k_sketch_feILi8ELi1EEEvNS_10SketchArgsE"}, others
+
+
 def test_gc_and_ot_expand_kernels_do_not_spill():
     """k_gc_garble / k_gc_eval at every share-string width b = 1..8, the garbled-table kernels and both
     OT expands (ChaCha12 since r06) stay in registers at >= 4 waves per SIMD."""
