@@ -57,6 +57,7 @@ EXPORTS = [
     "fhh_cot_extend_host", "fhh_cot_extend_ss_host", "fhh_gc_cot_host", "fhh_gt_cot_host", "fhh_gt_cot_ring32_host",
     "fhh_shard_plan", "fhh_reserve_clients", "fhh_add_keys_bincode_append",
     "fhh_bincode_request_bytes", "fhh_export_keys_bincode",
+    "fhh_frontier_plan", "fhh_tree_init_at", "fhh_frontier_paths",
 ]
 
 
@@ -320,6 +321,9 @@ def lib():
         "fhh_num_clients": (i, [vp, u64p]),
         "fhh_export_keys": (i, [vp, u8p, u8p, u8p, u8p]),
         "fhh_tree_init": (i, [vp]),
+        "fhh_frontier_plan": (i, [u32, u32, u64, u8p, u32p, u32p]),
+        "fhh_tree_init_at": (i, [vp, u64, u32, u8p]),
+        "fhh_frontier_paths": (i, [vp, u64p, u32p, u8p]),
         "fhh_tree_crawl": (i, [vp, u64p, u64p]),
         "fhh_tree_crawl_last": (i, [vp, u64p, u64p]),
         "fhh_node_sums_fe": (i, [vp, u64p, u64p]),

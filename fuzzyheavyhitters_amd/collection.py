@@ -165,6 +165,46 @@ class KeyCollection:
     def tree_init(self):
         self._chk(lib().fhh_tree_init(self._h))
 
+    def _paths_array(self, paths) -> np.ndarray:
+        """A frontier as uint8 [F][d][depth]: an array of that shape, or nodes given as d tuples of direction bits
+        (what `workload.plaintext_crawl` returns; one node `((), ...)` of empty tuples is the root)."""
+        a = np.asarray(paths if isinstance(paths, np.ndarray) else [[list(p) for p in node] for node in paths])
+        if a.ndim == 2 and a.shape[1] == self.n_dims and a.size == 0:
+            a = a.reshape(a.shape[0], self.n_dims, 0)
+        if a.ndim != 3 or a.shape[1] != self.n_dims:
+            raise FhhError(f"paths must be [F][{self.n_dims}][depth], got shape {a.shape}")
+        return np.ascontiguousarray(a, np.uint8)
+
+    def tree_init_at(self, paths):
+        """`tree_init` at a given frontier instead of the root (fhh_tree_init_at): node k of the frontier is
+        paths[k], the next `tree_crawl` runs level `depth`. A checkpoint taken with `frontier_paths` is restored
+        this way; candidate prefixes are counted by seeding their parents and crawling once."""
+        a = self._paths_array(paths)
+        self._chk(lib().fhh_tree_init_at(self._h, a.shape[0], a.shape[2], ptr(a) if a.size else None))
+
+    def frontier_paths(self) -> np.ndarray:
+        """uint8 [F][d][depth]: the paths of the nodes `frontier_size` counts in its first value (after an
+        unpruned `tree_crawl` the pending children, in `export_states`' order)."""
+        nn, dep = ctypes.c_uint64(), ctypes.c_uint32()
+        self._chk(lib().fhh_frontier_paths(self._h, ctypes.byref(nn), ctypes.byref(dep), None))
+        out = np.zeros((int(nn.value), self.n_dims, int(dep.value)), np.uint8)
+        if out.size:
+            self._chk(lib().fhh_frontier_paths(self._h, ctypes.byref(nn), ctypes.byref(dep), ptr(out)))
+        return out
+
+    @staticmethod
+    def frontier_plan(paths: np.ndarray):
+        """fhh_frontier_plan (host arithmetic): (n_unique [d], pos [F][d]) of paths uint8 [F][d][depth]."""
+        a = np.ascontiguousarray(paths, np.uint8)
+        if a.ndim != 3:
+            raise FhhError(f"paths must be [F][d][depth], got shape {a.shape}")
+        F, d, depth = a.shape
+        nu = np.zeros(max(d, 1), np.uint32)
+        pos = np.zeros((F, d), np.uint32)
+        check(lib().fhh_frontier_plan(d, depth, F, ptr(a) if a.size else None, ptr(nu, u32p),
+                                      ptr(pos, u32p) if pos.size else None))
+        return nu[:d], pos
+
     def _crawl(self, fn, share_planes: bool):
         nch = ctypes.c_uint64()
         if not share_planes:

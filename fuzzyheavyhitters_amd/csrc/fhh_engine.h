@@ -290,6 +290,20 @@ int node_partials(fhh_ctx* ctx, const void* vals, uint32_t fmt, uint64_t ld, uin
 int node_sums_finish(fhh_ctx* ctx, const uint64_t* partials, uint32_t fmt, void* out_a, void* out_b);
 bool fmt_is_fe255(uint32_t fmt);
 
+// fhh_frontier_plan's computation: a frontier given as paths [n_nodes][d][depth] (bytes 0/1) in the engine's
+// per-dim, de-duplicated form, and its trie as `hist` holds a crawl's history
+struct FrontierPlan {
+    std::vector<uint32_t> n_unique;              // [d] distinct dim-j prefixes
+    std::vector<uint32_t> pos;                   // [n_nodes][d] index of the node's dim-j prefix, first-appearance order
+    std::vector<std::vector<uint64_t>> rep;      // [d][n_unique[j]] the first node that carries the prefix
+    std::vector<std::vector<std::pair<uint32_t, uint32_t>>> hist;   // per depth: the distinct nodes as (parent, i)
+};
+// false (with the reason in *err) for the arguments fhh_tree_init_at refuses, data_len apart
+bool frontier_plan(uint32_t d, uint32_t depth, uint64_t n_nodes, const uint8_t* paths, FrontierPlan& plan,
+                   std::string* err);
+// fhh_tree_init_at on a one-GPU ctx with the plan made (a multi-device ctx plans once for its shards)
+int tree_init_at_planned(fhh_ctx* ctx, const FrontierPlan& plan, uint64_t n_nodes, uint32_t depth, const uint8_t* paths);
+
 // ---- fhh_keys_io.cpp -------------------------------------------------------------------------
 // the add_keys RPC payload's n client records (without the leading u64), decoded on the device
 int add_keys_bincode_records(fhh_ctx* ctx, uint64_t n, const uint8_t* recs);
@@ -327,6 +341,7 @@ int group_export_keys(fhh_ctx* g, uint8_t* key_idx, uint8_t* root_seed, uint8_t*
 int group_export_keys_bincode(fhh_ctx* g, uint64_t first, uint64_t count, uint64_t batch, uint8_t* out, uint64_t cap,
                               uint64_t* len);
 int group_tree_init(fhh_ctx* g);
+int group_tree_init_at(fhh_ctx* g, const FrontierPlan& plan, uint64_t n_nodes, uint32_t depth, const uint8_t* paths);
 int group_tree_crawl(fhh_ctx* g, bool last, uint64_t* n_children, uint64_t* planes);
 int group_node_sums(fhh_ctx* g, const void* const* vals, bool host, uint64_t ld, uint32_t fmt, void* out_a,
                     void* out_b);

@@ -395,7 +395,9 @@ int group_export_keys_bincode(fhh_ctx* g, uint64_t first, uint64_t count, uint64
     });
 }
 
-int group_tree_init(fhh_ctx* g) {
+// the keys in place on the shards for a tree_init: staged add_keys keys are cut into the shards' ranges, appended
+// ones must be complete
+static int place_keys(fhh_ctx* g, const char* who) {
     Group& G = *g->group;
     if (g->h_n) {
         // keys staged by add_keys: cut them into the shards' client ranges now that n is known
@@ -427,11 +429,26 @@ int group_tree_init(fhh_ctx* g) {
         g->h_n = 0;
         set_bases(G);
     }
-    if (!G.placed) return g->fail(FHH_E_STATE, "tree_init with no keys (collect.rs:83)");
+    if (!G.placed) return g->fail(FHH_E_STATE, std::string(who) + " with no keys (collect.rs:83)");
     if (G.appended && G.app_n != G.reserved)
-        return g->fail(FHH_E_STATE, "tree_init: " + std::to_string(G.app_n) + " clients appended of the " +
+        return g->fail(FHH_E_STATE, std::string(who) + ": " + std::to_string(G.app_n) + " clients appended of the " +
                                         std::to_string(G.reserved) + " reserved (the shards' ranges are fixed by the reservation)");
-    int rc = fan_out(g, [&](size_t, fhh_ctx* s) { return fhh_tree_init(s); });
+    return FHH_OK;
+}
+
+int group_tree_init(fhh_ctx* g) {
+    int rc = place_keys(g, "tree_init");
+    if (rc) return rc;
+    rc = fan_out(g, [&](size_t, fhh_ctx* s) { return fhh_tree_init(s); });
+    if (rc) return rc;
+    return ensure_comms(g);
+}
+
+// every shard gets the same plan and walks its own clients' keys (a shard without clients takes no part)
+int group_tree_init_at(fhh_ctx* g, const FrontierPlan& plan, uint64_t n_nodes, uint32_t depth, const uint8_t* paths) {
+    int rc = place_keys(g, "tree_init_at");
+    if (rc) return rc;
+    rc = fan_out(g, [&](size_t, fhh_ctx* s) { return tree_init_at_planned(s, plan, n_nodes, depth, paths); });
     if (rc) return rc;
     return ensure_comms(g);
 }

@@ -481,6 +481,158 @@ int node_sums_finish(fhh_ctx* ctx, const uint64_t* h, uint32_t fmt, void* out_a,
     return FHH_OK;
 }
 
+// One trie walk per dim and one over whole nodes, level by level: a prefix's id at depth lv + 1 is the rank of
+// its (id at depth lv, next direction) among those seen so far, so the ids at the last depth number the distinct
+// prefixes in order of first appearance without hashing a path.
+bool frontier_plan(uint32_t d, uint32_t depth, uint64_t n_nodes, const uint8_t* paths, FrontierPlan& plan,
+                   std::string* err) {
+    auto refuse = [&](const std::string& m) {
+        if (err) *err = m;
+        return false;
+    };
+    if (d < 1 || d > (uint32_t)kMaxDims) return refuse("n_dims must be in [1, " + std::to_string(kMaxDims) + "]");
+    if (n_nodes == 0) return refuse("n_nodes = 0: a frontier holds at least one node");
+    if (n_nodes >> (32 - d)) return refuse("n_nodes << n_dims does not fit the engine's u32 child indices");
+    if (depth && !paths) return refuse("NULL paths with depth > 0");
+    const size_t total = (size_t)n_nodes * d * depth;
+    for (size_t k = 0; k < total; k++)
+        if (paths[k] > 1)
+            return refuse("paths byte " + std::to_string(k) + " is " + std::to_string(paths[k]) + ", not 0 or 1");
+    if (depth == 0 && n_nodes > 1) return refuse("node 1 repeats the path of node 0 (the root)");
+
+    const uint32_t F = (uint32_t)n_nodes;
+    std::vector<uint32_t> cur(F);
+    std::vector<int32_t> remap;
+    // one level: every node's id (cur) at depth lv + 1 from its id at depth lv, one of `count`, and its next
+    // direction(s) key(k) < 2^width; returns the count of distinct ids, on_new(k, parent, key) at each first
+    // appearance
+    auto step = [&](uint32_t width, uint32_t count, auto key, auto on_new) {
+        remap.assign((size_t)count << width, -1);
+        uint32_t next = 0;
+        for (uint32_t k = 0; k < F; k++) {
+            const uint32_t kv = key(k);
+            int32_t& r = remap[((size_t)cur[k] << width) | kv];
+            if (r < 0) {
+                r = (int32_t)next++;
+                on_new(k, cur[k], kv);
+            }
+            cur[k] = (uint32_t)r;
+        }
+        return next;
+    };
+    plan.n_unique.assign(d, 1);
+    plan.pos.assign((size_t)F * d, 0);
+    plan.rep.assign(d, {});
+    for (uint32_t j = 0; j < d; j++) {
+        std::fill(cur.begin(), cur.end(), 0u);
+        uint32_t count = 1;
+        for (uint32_t lv = 0; lv < depth; lv++)
+            count = step(1, count, [&](uint32_t k) { return (uint32_t)paths[((size_t)k * d + j) * depth + lv]; },
+                         [](uint32_t, uint32_t, uint32_t) {});
+        plan.n_unique[j] = count;
+        plan.rep[j].assign(count, ~0ull);
+        for (uint32_t k = 0; k < F; k++) {
+            plan.pos[(size_t)k * d + j] = cur[k];
+            if (plan.rep[j][cur[k]] == ~0ull) plan.rep[j][cur[k]] = k;
+        }
+    }
+    // whole nodes: the trie of the paths, row lv = the distinct nodes of depth lv + 1 as (parent, i)
+    plan.hist.assign(depth, {});
+    std::fill(cur.begin(), cur.end(), 0u);
+    uint32_t count = 1;
+    for (uint32_t lv = 0; lv < depth; lv++) {
+        auto& row = plan.hist[lv];
+        count = step(d, count,
+                     [&](uint32_t k) {
+                         uint32_t i = 0;
+                         for (uint32_t j = 0; j < d; j++) i |= (uint32_t)paths[((size_t)k * d + j) * depth + lv] << j;
+                         return i;
+                     },
+                     [&](uint32_t, uint32_t parent, uint32_t i) { row.emplace_back(parent, i); });
+    }
+    if (depth && count != F) {
+        // the reference's frontier never holds a node twice; a second copy would be counted twice
+        std::vector<int64_t> first(count, -1);
+        for (uint32_t k = 0; k < F; k++) {
+            if (first[cur[k]] >= 0)
+                return refuse("node " + std::to_string(k) + " repeats the path of node " + std::to_string(first[cur[k]]));
+            first[cur[k]] = k;
+        }
+    }
+    return true;
+}
+
+int tree_init_at_planned(fhh_ctx* ctx, const FrontierPlan& plan, uint64_t n_nodes, uint32_t depth, const uint8_t* paths) {
+    int rc = ctx_set_device(ctx);
+    if (rc) return rc;
+    rc = upload_staged_keys(ctx);
+    if (rc) return rc;
+    if (!ctx->dev_keys || ctx->n == 0) return ctx->fail(FHH_E_STATE, "tree_init_at with no keys (collect.rs:83)");
+    if (ctx->appended) {
+        rc = finish_appended(ctx);
+        if (rc) return rc;
+    }
+    const uint32_t d = ctx->d, dir_words = (depth + 31) / 32;
+    // the distinct prefixes' direction bits, every dim's in one upload: [dim][prefix][dir_words]
+    std::vector<uint32_t> dirs;
+    size_t dirs_off[kMaxDims] = {};
+    for (uint32_t j = 0; j < d; j++) {
+        dirs_off[j] = dirs.size();
+        dirs.resize(dirs.size() + (size_t)plan.n_unique[j] * dir_words, 0u);
+        for (uint32_t e = 0; e < plan.n_unique[j]; e++) {
+            const uint8_t* p = paths + ((size_t)plan.rep[j][e] * d + j) * depth;
+            uint32_t* w = dirs.data() + dirs_off[j] + (size_t)e * dir_words;
+            for (uint32_t l = 0; l < depth; l++) w[l >> 5] |= (uint32_t)p[l] << (l & 31);
+        }
+    }
+    rc = upload_u32(ctx, ctx->lists, dirs);   // (the next crawl's upload_lists reuses the buffer: this call drains the stream)
+    if (rc) return rc;
+    EvalPathsArgs a{};
+    a.cw_seed = ctx->cw_seed.as<uint4>();
+    a.cw_bits = ctx->cw_bits.as<uint64_t>();
+    a.root_seed = ctx->root_seed.as<uint4>();
+    a.key_idx = ctx->key_idx.as<uint64_t>();
+    a.d = d;
+    a.K = ctx->K;
+    a.npad = (uint32_t)ctx->npad;
+    a.nw = (uint32_t)ctx->nw;
+    a.depth = depth;
+    a.dir_words = dir_words;
+    uint64_t entries = 0;
+    for (uint32_t j = 0; j < d; j++) {
+        DimTable& T = ctx->tab[j];
+        T.cur = 0;
+        rc = table_ensure(ctx, T, 0, plan.n_unique[j]);
+        if (rc) return rc;
+        EvalPathsJob& J = a.job[j];
+        J.dst_seed = T.seed[0].as<uint4>();
+        J.dst_t = T.t[0].as<uint64_t>();
+        J.dst_y = T.y[0].as<uint64_t>();
+        J.dirs = ctx->lists.as<uint32_t>() + dirs_off[j];
+        J.n_prefixes = plan.n_unique[j];
+        J.item_begin = a.total_items;
+        a.total_items += (uint64_t)2 * ctx->nw * ((plan.n_unique[j] + kEvalPathsP - 1) / kEvalPathsP);
+        entries += plan.n_unique[j];
+    }
+    HIP_TRY(ctx, launch_eval_paths(a, ctx->grid, ctx->stream));
+    for (uint32_t j = 0; j < d; j++) {
+        ctx->tab[j].live.resize(plan.n_unique[j]);
+        for (uint32_t e = 0; e < plan.n_unique[j]; e++) ctx->tab[j].live[e] = e;
+    }
+    ctx->frontier.assign(n_nodes, Node{});
+    for (uint64_t k = 0; k < n_nodes; k++)
+        for (uint32_t j = 0; j < d; j++) ctx->frontier[k].pos[j] = plan.pos[k * d + j];
+    ctx->hist = plan.hist;
+    ctx->last_nodes.clear();
+    ctx->last_values.clear();
+    ctx->last_hist.clear();
+    ctx->level = depth;
+    ctx->pending_C = 0;
+    ctx->phase = Phase::kFrontier;
+    ctx->stats.aes_blocks += (uint64_t)depth * 2 * entries * ctx->n;   // the blocks executed: one per (prefix, key, level)
+    return ctx_sync(ctx);
+}
+
 }  // namespace eng
 }  // namespace fhh
 
@@ -747,6 +899,59 @@ int fhh_tree_init(fhh_ctx* ctx) {
     ctx->pending_C = 0;
     ctx->phase = Phase::kFrontier;
     return ctx_sync(ctx);
+}
+
+int fhh_frontier_plan(uint32_t n_dims, uint32_t depth, uint64_t n_nodes, const uint8_t* paths, uint32_t* n_unique,
+                      uint32_t* pos) {
+    FrontierPlan plan;
+    std::string why;
+    if (!frontier_plan(n_dims, depth, n_nodes, paths, plan, &why)) {
+        g_err = "frontier_plan: " + why;
+        return FHH_E_ARG;
+    }
+    if (n_unique) std::memcpy(n_unique, plan.n_unique.data(), plan.n_unique.size() * 4);
+    if (pos) std::memcpy(pos, plan.pos.data(), plan.pos.size() * 4);
+    return FHH_OK;
+}
+
+int fhh_tree_init_at(fhh_ctx* ctx, uint64_t n_nodes, uint32_t depth, const uint8_t* paths) {
+    CTX_CHECK(ctx);
+    // every refusal of the arguments comes before the ctx is touched
+    if (depth >= ctx->L)
+        return ctx->fail(FHH_E_ARG, "tree_init_at: depth " + std::to_string(depth) + " >= data_len " +
+                                        std::to_string(ctx->L) + " (no CorWord left to crawl)");
+    FrontierPlan plan;
+    std::string why;
+    if (!frontier_plan(ctx->d, depth, n_nodes, paths, plan, &why)) return ctx->fail(FHH_E_ARG, "tree_init_at: " + why);
+    if (ctx->group) return group_tree_init_at(ctx, plan, n_nodes, depth, paths);
+    return tree_init_at_planned(ctx, plan, n_nodes, depth, paths);
+}
+
+int fhh_frontier_paths(fhh_ctx* ctx, uint64_t* n_nodes, uint32_t* depth, uint8_t* paths) {
+    CTX_CHECK(ctx);
+    if (ctx->group) {
+        fhh_ctx* lead = group_lead(ctx);
+        if (!lead) return ctx->fail(FHH_E_STATE, "frontier_paths before tree_init");
+        const int rc = fhh_frontier_paths(lead, n_nodes, depth, paths);
+        if (rc) ctx->fail(rc, lead->err);
+        return rc;
+    }
+    if (ctx->phase == Phase::kNoInit) return ctx->fail(FHH_E_STATE, "frontier_paths before tree_init");
+    // the nodes fhh_frontier_size counts: an unpruned tree_crawl's children, else the frontier
+    const bool pending = ctx->phase == Phase::kPending;
+    const uint64_t F = pending ? ctx->pending_C : ctx->frontier.size();
+    const uint32_t len = pending ? ctx->level + 1 : ctx->level, d = ctx->d;
+    if (n_nodes) *n_nodes = F;
+    if (depth) *depth = len;
+    if (!paths || len == 0) return FHH_OK;
+    if (ctx->hist.size() < (pending ? len - 1 : len) || (!pending && ctx->hist[len - 1].size() != F))
+        return ctx->fail(FHH_E_STATE, "frontier_paths: the crawl history does not cover the frontier");
+    for (uint64_t k = 0; k < F; k++) {
+        const std::pair<uint32_t, uint32_t> pi =
+            pending ? std::make_pair((uint32_t)(k >> d), (uint32_t)(k & ((1u << d) - 1))) : ctx->hist[len - 1][k];
+        node_path(ctx->hist, len - 1, pi.first, pi.second, d, paths + k * d * len);
+    }
+    return FHH_OK;
 }
 
 int fhh_tree_crawl(fhh_ctx* ctx, uint64_t* n_children, uint64_t* share_planes) {

@@ -300,7 +300,33 @@ struct KeygenArgs {
     uint32_t d, L, K, npad, nw;
 };
 
+// k_eval_paths (fhh_tree_init_at): every client's keys walked from the root to given prefixes. Job j = dim j's
+// distinct prefixes, written as entries 0 .. n_prefixes - 1 of the dim's table; an item is one word (64
+// clients) of one side of kEvalPathsP prefixes: job j has 2 nw ceil(n_prefixes / kEvalPathsP) items.
+constexpr int kEvalPathsP = 4;
+struct EvalPathsJob {
+    uint4* dst_seed;            // [n_prefixes][2][npad]
+    uint64_t* dst_t;            // [n_prefixes][2][nw]
+    uint64_t* dst_y;
+    const uint32_t* dirs;       // [n_prefixes][dir_words]: direction of level l = bit l % 32 of word l / 32
+    uint32_t n_prefixes;
+    uint64_t item_begin;        // the launch's first item of this job
+};
+struct EvalPathsArgs {
+    const uint4* cw_seed;
+    const uint64_t* cw_bits;
+    const uint4* root_seed;
+    const uint64_t* key_idx;
+    EvalPathsJob job[kMaxDims];
+    uint32_t d, K, npad, nw;
+    uint32_t depth;             // levels walked (< L)
+    uint32_t dir_words;         // ceil(depth / 32)
+    uint64_t total_items;
+};
+
 // ---- launch wrappers (fhh_kernels.hip); all asynchronous on `stream` ----
+// grid: at most this many workgroups (the persistent k_expand grid; the items are dealt grid-stride)
+hipError_t launch_eval_paths(const EvalPathsArgs& a, int grid, hipStream_t stream);
 // seq: the counter's launch count (fhh_ctx::expand_seq), advanced per k_expand launch
 hipError_t launch_expand(const ExpandLaunch& a, int variant, int grid, uint32_t* work_counter, uint32_t* seq,
                          hipStream_t stream);

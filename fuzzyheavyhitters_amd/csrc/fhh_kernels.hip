@@ -12,6 +12,7 @@
 //   k_sum_fe*       per-child sums of host-provided FE / FE255 values (collect.rs:487-501)
 //   k_keygen        batched gen_interval keygen (ibDCF.rs:84-173)
 //   k_init_table    eval_init for every key (ibDCF.rs:229-236, collect.rs:67-92)
+//   k_eval_paths    eval_ibDCF at given prefixes (ibDCF.rs:238-250): fhh_tree_init_at's frontier
 //   k_keys_from_aos add_key wire layout -> SoA device layout
 #include "fhh_internal.h"
 #include "expand_kernel.h"
@@ -829,6 +830,135 @@ hipError_t launch_init_tables(const uint4* root, const uint64_t* key_idx, uint32
     unsigned blocks = (unsigned)((total + 255) / 256);
     if (blocks > 4096) blocks = 4096;
     hipLaunchKernelGGL(k_init_table, dim3(blocks), dim3(256), 0, stream, root, key_idx, dim, npad, nw, seed, t, y);
+    return hipGetLastError();
+}
+
+// --------------------------------------------------------------------------------------
+// k_eval_paths: eval_ibDCF (ibDCF.rs:238-250) of every client's keys at given prefixes — fhh_tree_init_at.
+// One wave = 64 consecutive clients (word w) of one (dim j, side s, group of kEvalPathsP distinct dim-j
+// prefixes); one lane = one client. The lane walks the group's prefixes from the root down `depth` levels
+// with their seeds in registers: one AES block per (prefix, key, level), the 4 prefixes' blocks in lockstep
+// (k_expand spends four per entry and level, both directions of both sides, and stores every child seed).
+// The level's CorWord seed is loaded once for the 4 prefixes (4 B per AES block); its bit words, the t / y
+// words and the direction bits (packed per prefix, bit l % 32 of word l / 32) are wave-uniform and go
+// through the scalar path. Level l + 1's CorWord is requested before level l's AES. Lanes past n do what
+// they do in k_init_table / k_expand: the same arithmetic on the padding's (zero) keys. A partial last
+// group repeats its last prefix in the idle slots and stores only the prefixes that exist.
+// k_expand's launch shape: 1024 threads share the 128 KiB of tables, 4 waves per SIMD; every item costs
+// the same, so the items are dealt grid-stride.
+// --------------------------------------------------------------------------------------
+__global__ __launch_bounds__(kExpandBlock, 1) void k_eval_paths(EvalPathsArgs a) {
+    __shared__ uint32_t tbl[ExpandTab::kWords];
+    for (int i = threadIdx.x; i < ExpandTab::kWords; i += kExpandBlock) tbl[i] = ExpandTab::word(c_T0.v, i);
+    __syncthreads();
+
+    constexpr int P = kEvalPathsP;
+    const uint32_t lane = threadIdx.x & 63;
+    uint32_t b0, b1;
+    ExpandTab::bases(lane, b0, b1);
+    const uint64_t wpb = kExpandBlock / 64;
+    const uint64_t nwaves = (uint64_t)gridDim.x * wpb;
+    const size_t npad = a.npad, nw = a.nw;
+    for (uint64_t item = (uint64_t)blockIdx.x * wpb + wave_id_uniform(); item < a.total_items; item += nwaves) {
+        uint32_t j = 0;
+        while (j + 1 < a.d && item >= a.job[j + 1].item_begin) j++;
+        const EvalPathsJob& J = a.job[j];
+        // item = (group * 2 + side) * nw + word: a workgroup's waves read neighbouring words of one CorWord row
+        const uint64_t local = item - J.item_begin;
+        const uint32_t w = (uint32_t)(local % nw);
+        const uint32_t gs = (uint32_t)(local / nw);
+        const uint32_t s = gs & 1u, e0 = (gs >> 1) * P;
+        const uint32_t c = w * 64 + lane;
+        const size_t kk = 2 * j + s;
+
+        // eval_init (ibDCF.rs:229-236): seed = root_seed, t = y = key_idx
+        const uint4 root = a.root_seed[kk * npad + c];
+        const uint64_t kidx = uniform_load(a.key_idx, kk * nw + w);
+        uint32_t sd[P][4];
+        uint64_t tw[P], yw[P];
+        const uint32_t* dirs[P];
+#pragma unroll
+        for (int p = 0; p < P; p++) {
+            sd[p][0] = root.x; sd[p][1] = root.y; sd[p][2] = root.z; sd[p][3] = root.w;
+            tw[p] = yw[p] = kidx;
+            const uint32_t e = e0 + p < J.n_prefixes ? e0 + p : J.n_prefixes - 1;
+            dirs[p] = J.dirs + (size_t)e * a.dir_words;
+        }
+
+        uint4 cw = make_uint4(0, 0, 0, 0);
+        uint64_t cwp[4] = {0, 0, 0, 0};
+        if (a.depth) {
+            cw = a.cw_seed[kk * npad + c];
+#pragma unroll
+            for (int b = 0; b < 4; b++) cwp[b] = uniform_load(a.cw_bits, (kk * 4 + b) * nw + w);
+        }
+        uint32_t dw[P] = {};
+        for (uint32_t l = 0; l < a.depth; l++) {
+            if ((l & 31u) == 0) {
+#pragma unroll
+                for (int p = 0; p < P; p++) dw[p] = uniform_load(dirs[p], l >> 5);
+            }
+            // the next level's CorWord (ibDCF.rs:215-217 `cor_words[state.level]`), off the dependent chain
+            uint4 cwn = cw;
+            uint64_t cwpn[4] = {cwp[0], cwp[1], cwp[2], cwp[3]};
+            if (l + 1 < a.depth) {
+                const size_t krow = (size_t)(l + 1) * a.K + kk;
+                cwn = a.cw_seed[krow * npad + c];
+#pragma unroll
+                for (int b = 0; b < 4; b++) cwpn[b] = uniform_load(a.cw_bits, (krow * 4 + b) * nw + w);
+            }
+            uint32_t blk[P][4];
+            uint64_t pb[P], py[P];
+            uint32_t dir[P];
+#pragma unroll
+            for (int p = 0; p < P; p++) {
+                dir[p] = (dw[p] >> (l & 31u)) & 1u;
+                prg_ctr(sd[p], (int)dir[p], blk[p]);
+                uint32_t bit, ybit;
+                prg_ctrl_bits(blk[p][0], (int)dir[p], bit, ybit);
+                pb[p] = __ballot(bit);
+                py[p] = __ballot(ybit);
+            }
+            aes0_mmo_tab<DevOpsX, ExpandTab, P>(blk, tbl, b0, b1);
+#pragma unroll
+            for (int p = 0; p < P; p++) {
+                const uint32_t tmask = 0u - (uint32_t)((tw[p] >> lane) & 1);   // if state.bit
+                sd[p][0] = blk[p][0] ^ (cw.x & tmask);
+                sd[p][1] = blk[p][1] ^ (cw.y & tmask);
+                sd[p][2] = blk[p][2] ^ (cw.z & tmask);
+                sd[p][3] = blk[p][3] ^ (cw.w & tmask);
+                // new_bit = tau.bits[dir] ^ (t & cw.bits[dir]);
+                // new_y = tau.y_bits[dir] ^ (t & cw.y_bits[dir]) ^ y   (ibDCF.rs:211-219)
+                const uint64_t cb = dir[p] ? cwp[1] : cwp[0], cy = dir[p] ? cwp[3] : cwp[2];
+                yw[p] = py[p] ^ (tw[p] & cy) ^ yw[p];
+                tw[p] = pb[p] ^ (tw[p] & cb);
+            }
+            cw = cwn;
+#pragma unroll
+            for (int b = 0; b < 4; b++) cwp[b] = cwpn[b];
+        }
+
+#pragma unroll
+        for (int p = 0; p < P; p++) {
+            const uint32_t e = e0 + p;
+            if (e < J.n_prefixes) {   // wave-uniform
+                const size_t row = (size_t)2 * e + s;
+                J.dst_seed[row * npad + c] = make_uint4(sd[p][0], sd[p][1], sd[p][2], sd[p][3]);
+                if (lane == 0) {
+                    J.dst_t[row * nw + w] = tw[p];
+                    J.dst_y[row * nw + w] = yw[p];
+                }
+            }
+        }
+    }
+}
+
+hipError_t launch_eval_paths(const EvalPathsArgs& a, int grid, hipStream_t stream) {
+    if (a.total_items == 0) return hipSuccess;
+    const uint64_t wpb = kExpandBlock / 64;
+    const uint64_t blocks_needed = (a.total_items + wpb - 1) / wpb;
+    const int g = (int)(blocks_needed < (uint64_t)grid ? blocks_needed : (uint64_t)grid);
+    hipLaunchKernelGGL(k_eval_paths, dim3(g), dim3(kExpandBlock), 0, stream, a);
     return hipGetLastError();
 }
 

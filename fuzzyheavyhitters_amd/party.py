@@ -248,7 +248,7 @@ def two_party_crawl(c0: KeyCollection, c1: KeyCollection, threshold: float, ncli
                     chunk_children: int | None = None, chunk_bytes: int = 64 << 30,
                     level_log: list | None = None, base_ot_every: str = "level",
                     base_ot_workers: int | None = None, base_ot_ahead: int = 8,
-                    form: str = "table", ot_ss_k: int = 1) -> TwoPartyResult:
+                    form: str = "table", ot_ss_k: int = 1, start_paths=None) -> TwoPartyResult:
     """The leader's level loop (leader.rs:417-440) with the GC + OT of every level split between the
     two servers' ctxs (server 0 garbles / sends, server 1 evaluates / receives): crawl both, run the
     level's protocol through the channel, take each server's node sums from its own device
@@ -278,7 +278,12 @@ def two_party_crawl(c0: KeyCollection, c1: KeyCollection, threshold: float, ncli
     table with its shares in Z_2^32: half the gc bytes at the FE levels, whose sums the leader thresholds with
     keep_values_ring32 and whose recorded counts are (s0 - s1) mod 2^32; d <= 2 and a client total below 2^32
     only, ValueError otherwise) — a public protocol choice both parties and the leader make alike. `ot_ss_k` (r06, public like form): 1 = IKNP OT extension, 2 / 4 =
-    SoftSpoken with k = ot_ss_k (the U messages carry 128 / k rows + the GGM corrections)."""
+    SoftSpoken with k = ot_ss_k (the U messages carry 128 / k rows + the GGM corrections).
+
+    `start_paths` (None: the root): a frontier [F][d][depth], as `KeyCollection.tree_init_at` takes it — a
+    checkpoint's `frontier_paths`, or one part of a split prefix space. Both collections start there instead
+    of `tree_init` and the loop runs levels depth .. L - 1; the base OTs, `expect_counts` and `level_log` stay
+    indexed by the real level, and the per-level lists of the result hold those levels only."""
     if ot_ss_k not in (1, 2, 4):
         raise ValueError(f"two_party_crawl: ot_ss_k {ot_ss_k!r}")
     if material not in ("fresh", "test"):
@@ -295,6 +300,11 @@ def two_party_crawl(c0: KeyCollection, c1: KeyCollection, threshold: float, ncli
         raise ValueError(f"two_party_crawl: form 'table32' needs d <= 2 (no Z_2^32 form of the circuit), d = {c0.n_dims}")
     if ring32 and n_total >= 1 << 32:
         raise ValueError("two_party_crawl: form 'table32' needs a client total below 2^32")
+    if start_paths is not None:
+        start_paths = c0._paths_array(start_paths)
+        if start_paths.shape[2] >= L:
+            raise ValueError(f"two_party_crawl: start_paths of depth {start_paths.shape[2]} leave no level of {L} to run")
+    lv0 = 0 if start_paths is None else start_paths.shape[2]
     thr = max(1, int(threshold * n_total))
     thr_last = max(1, min(int(threshold * n_total), 0xFFFFFFFF))
     S = len(c0.shard_info()[0])
@@ -325,7 +335,7 @@ def two_party_crawl(c0: KeyCollection, c1: KeyCollection, threshold: float, ncli
                 if shard_clients[k] and (key, k) not in pending:
                     pending[(key, k)] = pool.submit(runs, k, kinds)
 
-        for lv in range(min(L, base_ot_ahead)):
+        for lv in range(lv0, min(L, lv0 + base_ot_ahead)):
             submit(lv)
 
     def level_base(lv, k):
@@ -337,8 +347,6 @@ def two_party_crawl(c0: KeyCollection, c1: KeyCollection, threshold: float, ncli
             del pending[(key, k)]
         return [g for g, _ in got], [e for _, e in got]
 
-    c0.tree_init()
-    c1.tree_init()
     from .fields import FE255_P, FE_P
     tm = timing if timing is not None else {}
     for k in ("crawl", "gcot", "node_sums", "keep", "prune"):
@@ -347,7 +355,13 @@ def two_party_crawl(c0: KeyCollection, c1: KeyCollection, threshold: float, ncli
     if chunk_children is None:
         chunk_children = max(1, chunk_bytes // (_PARTY_BYTES_PER_TEST * max(1, max(shard_clients))))
     try:
-        for lv in range(L):
+        if start_paths is not None:   # (inside the try: refused paths must not leave the base-OT pool running)
+            c0.tree_init_at(start_paths)
+            c1.tree_init_at(start_paths)
+        else:
+            c0.tree_init()
+            c1.tree_init()
+        for lv in range(lv0, L):
             last = lv == L - 1
             if pool is not None and lv + base_ot_ahead < L:
                 submit(lv + base_ot_ahead)

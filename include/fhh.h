@@ -189,6 +189,41 @@ int fhh_export_keys_bincode(fhh_ctx* ctx, uint64_t first, uint64_t count, uint64
 /* tree_init (collect.rs:67-92) with eval_init per key (ibDCF.rs:229-236). */
 int fhh_tree_init(fhh_ctx* ctx);
 
+/* tree_init at a given frontier instead of the root: checkpoint / resume of a crawl, counts at known candidates,
+ * a prefix space split between server pairs. The reference has no counterpart: its crawl starts at the root
+ * (collect.rs:67-92); a single prefix is its eval_ibDCF (ibDCF.rs:238-250), here for every client, key and
+ * given node in one kernel (k_eval_paths: one AES block per distinct dim-prefix, key and level, no
+ * intermediate state stored).
+ *   paths [n_nodes][d][depth] bytes 0/1, direction bits from the root down (fhh_final_shares' layout);
+ *   node k of the new frontier is paths[k]. depth = 0 with n_nodes = 1 is fhh_tree_init.
+ * Preconditions are fhh_tree_init's (staged fhh_add_keys keys are uploaded, appended batches finished;
+ * FHH_E_STATE with no keys), and like it the call may come in any phase: it replaces the frontier and drops
+ * frontier_last, its values and the crawl history. Afterwards the ctx is in the frontier phase at level =
+ * depth: the next fhh_tree_crawl reads CorWord index depth, and the two-party GC + OT calls,
+ * fhh_party_node_sums, prune and fhh_final_shares (full-length paths) go on as after an ordinary crawl to
+ * that frontier. FHH_E_ARG, with the ctx exactly as it was, for n_nodes = 0, depth >= data_len, a byte other
+ * than 0/1, two equal paths (the reference's frontier never holds a node twice; a second copy would be
+ * counted twice), n_nodes << d not fitting the engine's u32 child indices, NULL paths with depth > 0.
+ * fhh_stats: aes_blocks grows by depth * 2 * sum_j U_j * n, the blocks executed (U_j = dim j's distinct
+ * prefixes); levels, ref_evals and expand_launches do not change. On a multi-device ctx every shard walks
+ * its own clients to the same frontier. fhh_sim_crawl is the in-process harness: it always initialises at the
+ * root itself (fhh_sim_config has no start frontier).
+ *
+ * fhh_frontier_plan is the host arithmetic of that call, no device call (like fhh_shard_plan): n_unique[j] =
+ * U_j, pos[k][j] = the index of node k's dim-j prefix among dim j's distinct prefixes in order of first
+ * appearance (the engine keeps states per dim and de-duplicated). Either output may be NULL. FHH_E_ARG for
+ * the refusals above (data_len apart) and n_dims outside 1..4; fhh_last_error(NULL) explains. */
+int fhh_frontier_plan(uint32_t n_dims, uint32_t depth, uint64_t n_nodes, const uint8_t* paths, uint32_t* n_unique,
+                      uint32_t* pos);
+int fhh_tree_init_at(fhh_ctx* ctx, uint64_t n_nodes, uint32_t depth, const uint8_t* paths);
+
+/* The paths [n_nodes][d][depth] of the nodes fhh_frontier_size counts in n_frontier: the frontier, or after an
+ * unpruned fhh_tree_crawl its pending children (depth = level + 1), the nodes and order of
+ * fhh_export_states. A crawl's checkpoint: fhh_tree_init_at on these paths restores the evaluation states.
+ * NULL paths = query. FHH_E_STATE before any init; works after fhh_sim_crawl too (a multi-device ctx
+ * answers from its first shard with clients). */
+int fhh_frontier_paths(fhh_ctx* ctx, uint64_t* n_nodes, uint32_t* depth, uint8_t* paths);
+
 /* Frontier expansion of tree_crawl (collect.rs:379-418): evaluates every client's 2d keys
  * one level for every child of every frontier node. *n_children = C. share_planes (may be
  * NULL) receives [C][2d][nw] u64 — the GC input of collect.rs:415-418.
