@@ -20,6 +20,18 @@ class Result:
     value: int      # unreduced FieldElm sum as int (or count in plaintext-count harness mode)
 
 
+def _keep_bytes(keep) -> np.ndarray:
+    """A keep mask as the uint8 bytes the C ABI takes: bools, or integers passed on as they are (the library
+    refuses a byte other than 0/1). Other dtypes, and integers outside a byte, are refused here: a cast would
+    turn 0.5 or 256 into 0 silently."""
+    a = np.asarray(keep)
+    if a.dtype != np.bool_ and not np.issubdtype(a.dtype, np.integer):
+        raise FhhError(f"keep mask of dtype {a.dtype}: bools or integers 0/1 expected")
+    if a.dtype != np.bool_ and a.size and (a.min() < 0 or a.max() > 255):
+        raise FhhError("keep mask: an entry is not 0 or 1")
+    return np.ascontiguousarray(a.astype(np.uint8)).reshape(-1)
+
+
 class KeyCollection:
     """One server's key collection (collect.rs:45-1030) on one GPU, or — with `devices` — one
     collection whose clients are sharded over several GPUs (fhh_create_multi: contiguous ranges
@@ -157,6 +169,29 @@ class KeyCollection:
         self._chk(lib().fhh_export_keys_bincode(self._h, first, count, batch, ptr(out), out.size, ctypes.byref(got)))
         assert got.value == out.size
         return out
+
+    def retain_clients(self, keep):
+        """`apply_sketch_results` (main.rs:68-69): drop the clients whose keep entry is false (fhh_retain_clients).
+        Afterwards this is a collection of the survivors, in their old order, at the same frontier; both servers
+        call it with the same mask. keep: one 0/1 (or bool) entry per client."""
+        k = _keep_bytes(keep)
+        self._chk(lib().fhh_retain_clients(self._h, ptr(k) if k.size else None, k.size))
+
+    @staticmethod
+    def retain_plan(keep):
+        """fhh_retain_plan (host arithmetic): (n_kept, src) with src[k] = the old index of the k-th survivor."""
+        k = _keep_bytes(keep)
+        nk = ctypes.c_uint64()
+        src = np.zeros(max(k.size, 1), np.uint32)
+        check(lib().fhh_retain_plan(ptr(k) if k.size else None, k.size, ctypes.byref(nk), ptr(src, u32p)))
+        return int(nk.value), src[: nk.value].copy()
+
+    def retain_timing(self):
+        """((column ms, plane ms), (column bytes, plane bytes)) of the last retain_clients that ran its kernels."""
+        ms = (ctypes.c_double * 2)()
+        by = (ctypes.c_uint64 * 2)()
+        self._chk(lib().fhh_retain_timing(self._h, ms, by))
+        return (ms[0], ms[1]), (int(by[0]), int(by[1]))
 
     def set_client_base(self, base: int):
         self._chk(lib().fhh_set_client_base(self._h, base))

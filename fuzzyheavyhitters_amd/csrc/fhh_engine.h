@@ -1,6 +1,7 @@
 // Engine state shared by the host sources — not part of the public C ABI (include/fhh.h):
 //   fhh_host.cpp         one server's KeyCollection on one GPU (the engine core and its C ABI)
 //   fhh_keys_io.cpp      add_keys requests in bincode: decode, append and export
+//   fhh_retain.cpp       fhh_retain_clients: the collection compacted to the survivors of a keep mask
 //   fhh_sim_crawl.cpp    the in-process two-server harness: fhh_sim_*, the device-resident level loop
 //   fhh_sketch_host.cpp  sketch + Beaver verification wrappers
 //   fhh_group.cpp        one KeyCollection over several GPUs: clients sharded in 64-client words,
@@ -145,6 +146,10 @@ struct fhh_ctx {
     uint64_t reserved = 0;        // fhh_reserve_clients (0: none)
     DevBuf app_buf, app_err;      // a batch's payload and its error word, kept from call to call
     DevBuf emit_buf;              // fhh_export_keys_bincode: the serialized requests, kept from call to call
+    // the last fhh_retain_clients that ran its kernels here: column / plane gather time (HIP events) and the
+    // bytes they read plus wrote (fhh_retain_timing)
+    double retain_ms[2] = {0, 0};
+    uint64_t retain_bytes[2] = {0, 0};
     DimTable tab[kMaxDims];
 
     Phase phase = Phase::kNoInit;
@@ -326,7 +331,33 @@ int export_bincode_check(fhh_ctx* ctx, bool have_keys, uint64_t n, uint64_t firs
 int export_bincode_slice(fhh_ctx* ctx, uint64_t src_first, uint64_t m, uint64_t i0, uint64_t count, uint64_t B,
                          uint8_t* out);
 
+// ---- fhh_retain.cpp --------------------------------------------------------------------------
+// fhh_retain_plan's computation: false (with the reason in *err) for the masks it refuses
+bool retain_plan(const uint8_t* keep, uint64_t n, std::vector<uint32_t>& src, std::string* err);
+// The destination of one ctx's retain: everything the survivors' collection holds, built beside the ctx and
+// swapped in by retain_commit, so that a failure (and a multi-device ctx whose other shard fails) leaves the
+// ctx as it was.
+struct RetainStage {
+    uint64_t n2 = 0, nw2 = 0, npad2 = 0;
+    bool device = false;          // the ctx's keys are on the device (else staged by fhh_add_keys: the h_* vectors)
+    bool tables = false;          // frontier phase: every dim's live entries, made dense
+    std::vector<uint8_t> h_key_idx, h_root, h_cws, h_cwb;
+    DevBuf cw_seed, cw_bits, root_seed, key_idx, valid, lists;
+    DevBuf seed[kMaxDims], t[kMaxDims], y[kMaxDims];
+    size_t cap[kMaxDims] = {0, 0, 0, 0};
+    double ms[2] = {0, 0};
+    uint64_t bytes[2] = {0, 0};
+};
+int retain_check_state(fhh_ctx* ctx);   // FHH_E_STATE in the phases fhh_retain_clients refuses (one-GPU ctx)
+// gather the survivors src[0 .. n2) of a one-GPU ctx into `st` (allocated before the first launch; returns once
+// the stream has drained); the ctx is not changed
+int retain_prepare(fhh_ctx* ctx, const uint32_t* src, uint64_t n2, RetainStage& st);
+void retain_commit(fhh_ctx* ctx, RetainStage& st);   // host only: cannot fail
+// the survivors' records of add_keys-layout host vectors
+void retain_host_keys(const fhh_ctx* ctx, const uint32_t* src, uint64_t n2, RetainStage& st);
+
 // ---- fhh_group.cpp (multi-device ctx) --------------------------------------------------------
+int group_retain_clients(fhh_ctx* g, const uint8_t* keep, uint64_t n);
 void group_destroy(fhh_ctx* g);
 int group_reset(fhh_ctx* g);
 int group_set_client_base(fhh_ctx* g, uint64_t base);

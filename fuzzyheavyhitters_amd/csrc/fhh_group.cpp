@@ -460,13 +460,37 @@ int group_tree_crawl(fhh_ctx* g, bool last, uint64_t* n_children, uint64_t* plan
     group_num_clients(g, &n);
     const uint64_t nw = (n + 63) / 64;
     std::vector<uint64_t> C(G.shards.size(), 0);
+    const auto act = G.active();
+    // after fhh_retain_clients a shard's first client need not start a word: such shards write their planes to
+    // rows of their own and the host shifts them into place (the aligned case keeps the in-place copy)
+    bool ragged = false;
+    for (size_t k : act) ragged = ragged || G.base[k] % 64;
+    std::vector<std::vector<uint64_t>> own(G.shards.size());
     int rc = fan_out(g, [&](size_t k, fhh_ctx* s) {
         int r = ctx_set_device(s);
         if (r) return r;
-        return crawl_level(s, last, &C[k], planes, nw, G.base[k] / 64);
+        if (!planes || !ragged) return crawl_level(s, last, &C[k], planes, nw, G.base[k] / 64);
+        const uint64_t F = s->phase == Phase::kPending ? s->pending_C : s->frontier.size();
+        own[k].assign((size_t)(F << s->d) * 2 * s->d * s->nw, 0);
+        return crawl_level(s, last, &C[k], own[k].data(), s->nw, 0);
     });
     if (rc) return rc;
-    const auto act = G.active();
+    if (planes && ragged && !act.empty()) {
+        const size_t rows = (size_t)C[act[0]] * 2 * g->d;
+        std::memset(planes, 0, rows * nw * 8);
+        for (size_t k : act) {
+            if (C[k] != C[act[0]]) break;   // reported below
+            const uint64_t nwk = G.shards[k]->nw, w0 = G.base[k] / 64, sh = G.base[k] % 64;
+            for (size_t r = 0; r < rows; r++) {
+                const uint64_t* in = own[k].data() + r * nwk;
+                uint64_t* out = planes + r * nw + w0;
+                for (uint64_t i = 0; i < nwk; i++) {   // the lanes beyond the shard's clients are zero (k_share_planes)
+                    out[i] |= in[i] << sh;
+                    if (sh && w0 + i + 1 < nw) out[i + 1] |= in[i] >> (64 - sh);
+                }
+            }
+        }
+    }
     for (size_t k : act)
         if (C[k] != C[act[0]]) return g->fail(FHH_E_STATE, "tree_crawl: shards disagree on the frontier");
     if (n_children) *n_children = act.empty() ? 0 : C[act[0]];
@@ -536,6 +560,78 @@ int group_tree_prune(fhh_ctx* g, const uint8_t* keep, uint64_t n, bool last) {
         const int rc = last ? fhh_tree_prune_last(G.shards[k], keep, n) : fhh_tree_prune(G.shards[k], keep, n);
         if (rc) return shard_fail(g, k, rc);
     }
+    return FHH_OK;
+}
+
+// fhh_retain_clients on a multi-device ctx: each shard retains its own slice of the mask on its own GPU and
+// stream; the shards' ranges become the prefix sums of their survivor counts (no longer whole words: see
+// group_tree_crawl). Every shard gathers into buffers of its own first; they swap only when all have succeeded.
+int group_retain_clients(fhh_ctx* g, const uint8_t* keep, uint64_t n) {
+    Group& G = *g->group;
+    const size_t S = G.shards.size();
+    if (!G.placed && g->h_n == 0) return g->fail(FHH_E_STATE, "retain_clients: the ctx holds no keys");
+    if (G.placed) {
+        for (size_t k : G.active()) {
+            fhh_ctx* s = G.shards[k];
+            if (G.appended && s->phase == Phase::kNoInit)
+                return g->fail(FHH_E_STATE, "retain_clients: appended batches not yet finished by fhh_tree_init");
+            const int rc = retain_check_state(s);
+            if (rc) return shard_fail(g, k, rc);
+        }
+    }
+    std::vector<uint32_t> src;
+    std::string why;
+    if (!retain_plan(keep, n, src, &why)) return g->fail(FHH_E_ARG, "retain_clients: " + why);
+    uint64_t have = 0;
+    group_num_clients(g, &have);
+    if (n != have)
+        return g->fail(FHH_E_ARG, "retain_clients: keep.len() " + std::to_string(n) + " != " + std::to_string(have) +
+                                      " clients");
+    if (src.size() == n) return FHH_OK;
+    if (!G.placed) {   // still staged on the collection by fhh_add_keys
+        RetainStage st;
+        retain_host_keys(g, src.data(), src.size(), st);
+        retain_commit(g, st);
+        return FHH_OK;
+    }
+    std::vector<std::vector<uint32_t>> loc(S);   // each shard's survivors, as its own client indices
+    {
+        size_t k = 0;
+        for (uint32_t i : src) {
+            while (i >= G.base[k] + G.count[k]) k++;
+            loc[k].push_back((uint32_t)(i - G.base[k]));
+        }
+    }
+    std::vector<std::unique_ptr<RetainStage>> st(S);
+    for (auto& p : st) p.reset(new RetainStage());
+    auto partial = [&](size_t k) { return !loc[k].empty() && loc[k].size() != G.count[k]; };
+    const int rc = fan_out(g, [&](size_t k, fhh_ctx* s) {
+        if (!partial(k)) return (int)FHH_OK;
+        return retain_prepare(s, loc[k].data(), loc[k].size(), *st[k]);
+    });
+    if (rc) return rc;   // no shard has changed
+    g->retain_ms[0] = g->retain_ms[1] = 0;
+    g->retain_bytes[0] = g->retain_bytes[1] = 0;
+    uint64_t base = 0;
+    for (size_t k = 0; k < S; k++) {
+        fhh_ctx* s = G.shards[k];
+        if (partial(k)) {
+            retain_commit(s, *st[k]);
+            for (int i = 0; i < 2; i++) {
+                g->retain_ms[i] = std::max(g->retain_ms[i], s->retain_ms[i]);
+                g->retain_bytes[i] += s->retain_bytes[i];
+            }
+        } else if (G.count[k] && loc[k].empty()) {
+            (void)fhh_reset(s);   // no survivor: the empty-shard state (the shard takes no part from here on)
+        }
+        G.base[k] = base;
+        G.count[k] = loc[k].size();
+        base += G.count[k];
+    }
+    // the collection is now a placed one of n' clients, whatever path its keys came by
+    G.appended = false;
+    G.reserved = G.app_n = 0;
+    set_bases(G);
     return FHH_OK;
 }
 

@@ -366,6 +366,13 @@ hipError_t launch_repitch_seeds(const uint4* src, uint4* dst, uint64_t rows, uin
                                 uint64_t dst_pitch, hipStream_t stream);
 hipError_t launch_repitch_words(const uint64_t* src, uint64_t* dst, uint64_t rows, uint64_t width, uint64_t src_pitch,
                                 uint64_t dst_pitch, hipStream_t stream);
+// fhh_retain.hip (fhh_retain_clients): n_rows rows of the survivors idx[0 .. n2) (old client indices, increasing)
+// from row pitch npad / nw into a buffer of pitch npad2 / nw2, zero beyond n2; rows (may be null) = the source
+// row of each destination row. src and dst never overlap.
+hipError_t launch_retain_cols(const uint4* src, uint4* dst, const uint32_t* idx, const uint32_t* rows, uint64_t n_rows,
+                              uint64_t npad, uint64_t npad2, uint32_t n2, hipStream_t stream);
+hipError_t launch_retain_planes(const uint64_t* src, uint64_t* dst, const uint32_t* idx, const uint32_t* rows,
+                                uint64_t n_rows, uint64_t nw, uint64_t nw2, uint32_t n2, hipStream_t stream);
 // fhh_bincode_out.hip: clients [src_first, src_first + m) of the layout as clients [i0, i0 + m) of an export of
 // `count` clients in requests of B (bincode_emit.h); byte g of the export goes to stg[g - org], org % 4 == 0 and
 // org <= be_slice_begin(i0), stg holding be_slice_end(i0, m) - org bytes

@@ -513,6 +513,13 @@ int loop_setup(Loop& S) {
     const fhh_sim_config* cfg = S.cfg;
     const uint32_t d = S.d, levels = S.levels;
     uint32_t cap0 = std::max(cfg->init_capacity ? next_pow2(cfg->init_capacity) : 256u, c0->loop_cap_hint);
+    // keys still staged by fhh_add_keys go to the device first: until then npad is 0, and the tables grown
+    // below would be sized for no client while tree_init's roots are npad wide
+    for (fhh_ctx* c : S.cs)
+        if (c->h_n) {
+            const int rc = fhh_tree_init(c);
+            if (rc) return rc;
+        }
     // tables: both buffers of every dim of both servers hold >= E_cap entries
     for (fhh_ctx* c : S.cs)
         for (uint32_t j = 0; j < d; j++)

@@ -233,6 +233,19 @@ def sim_sketch_verify(kc, batch: DeviceSketchBatch, force_sequential: bool = Fal
     check(lib().fhh_sim_sketch_verify_fe(kc.handle, ctypes.byref(b)), kc.handle)
 
 
+def apply_sketch_results(c0, c1, ok) -> int:
+    """`col0.apply_sketch_results(&out); col1.apply_sketch_results(&out)` (main.rs:68-69): the clients whose
+    verification bit is false leave both servers' collections (KeyCollection.retain_clients with the same
+    mask). ok: one entry per client — `mul_verify`'s bools, or a level's row of a DeviceSketchBatch's `ok`
+    tensor. Returns the number of survivors."""
+    if hasattr(ok, "detach"):
+        ok = ok.detach().cpu().numpy()
+    keep = np.ascontiguousarray(np.asarray(ok).reshape(-1) != 0).astype(np.uint8)
+    c0.retain_clients(keep)
+    c1.retain_clients(keep)
+    return int(keep.sum())
+
+
 # ---- U = FieldElm: the last level (sketch_at_last, MulState<FieldElm>) -----------------------
 _P255_LIMBS = np.array([(FE255_P >> (32 * k)) & 0xFFFFFFFF for k in range(8)], np.int64)
 

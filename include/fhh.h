@@ -139,7 +139,9 @@ int fhh_create_multi(fhh_ctx** out, uint32_t data_len, uint32_t n_dims, const in
 #define FHH_REDUCE_HOST 1   /* partials summed on the host      */
 #define FHH_REDUCE_RCCL 2   /* in-process RCCL all-reduce       */
 /* Shard k of a collection (a one-GPU ctx is one shard): shard count, device, first client and
- * client count (0 before the keys are placed), and the reduction the collection uses. */
+ * client count (0 before the keys are placed), and the reduction the collection uses. After
+ * fhh_retain_clients the ranges are the prefix sums of the shards' survivor counts, no longer those of
+ * fhh_shard_plan. */
 int fhh_shard_info(const fhh_ctx* ctx, int shard, int* n_shards, int* device, uint64_t* client_base,
                    uint64_t* n_clients, int* reduction);
 /* The placement fhh_create_multi uses (host arithmetic, no device call): shard k of n_shards gets
@@ -223,6 +225,50 @@ int fhh_tree_init_at(fhh_ctx* ctx, uint64_t n_nodes, uint32_t depth, const uint8
  * NULL paths = query. FHH_E_STATE before any init; works after fhh_sim_crawl too (a multi-device ctx
  * answers from its first shard with clients). */
 int fhh_frontier_paths(fhh_ctx* ctx, uint64_t* n_nodes, uint32_t* depth, uint8_t* paths);
+
+/* apply_sketch_results (main.rs:68-69, "Causing key 3 and 7 to be removed", :63): keep[i] != 0 keeps client
+ * i, 0 drops it; n must equal fhh_num_clients. Both servers call it with the same mask, as the reference hands
+ * `out` to both collections — the `ok` bits of fhh_sim_sketch_verify_fe / _fe255 or fhh_mul_verify_*, or any
+ * other mask (revoked clients, duplicates, a closed collection window).
+ * Afterwards the ctx is a collection of the n' survivors in their old relative order: fhh_num_clients,
+ * fhh_export_keys(_bincode), fhh_export_states of the current frontier and every later crawl, share plane,
+ * sum, party message size and final share are those of a fresh ctx given only the survivors' keys and brought
+ * to the same frontier with fhh_tree_init_at(fhh_frontier_paths). The clients are removed physically (no
+ * "alive" flag that every sums path would have to read): two kernels gather the survivors' columns and
+ * bit-plane lanes into new buffers of the smaller layout (nw' = ceil(n' / 64), padding lanes zero, `valid`
+ * rebuilt) and the ctx swaps to them, so every later level costs n' clients. Never in place: peak extra
+ * device memory = the survivors' collection itself (their keys and the frontier's live table entries, n' / n
+ * of what the ctx holds); the old buffers are freed, the unused half of every table pair is released and
+ * re-sized by the next crawl.
+ * Unchanged: the frontier, its history and level, frontier_last and its recorded values, stats, client_base,
+ * the variant and grid settings, a party state between levels (its base-OT session counters included). Sums
+ * already returned for earlier levels, and the recorded frontier_last values, still include the dropped
+ * clients.
+ * Allowed with keys staged by fhh_add_keys (the host vectors are compacted), with keys on the device before
+ * fhh_tree_init (only the keys are compacted) and in the frontier phase (after an init, a prune,
+ * fhh_sim_crawl). FHH_E_STATE while a crawl's children are pending (prune first), with no keys, and on
+ * appended batches not yet finished by fhh_tree_init. FHH_E_ARG for n != fhh_num_clients and for the masks
+ * fhh_retain_plan refuses. Every refusal, and FHH_E_NOMEM (every destination is allocated before the first
+ * launch, the swap comes after the stream has drained), leaves the ctx exactly as it was. A mask of all ones
+ * returns FHH_OK without touching the device.
+ * On a multi-device ctx each shard retains its own slice of the mask on its own GPU; the shards' ranges
+ * become the prefix sums of their survivor counts, so fhh_shard_info no longer reports the ranges of
+ * fhh_shard_plan and a shard's first client need not start a 64-client word (the share planes of
+ * fhh_tree_crawl are then merged on the host, still [C][2d][ceil(n' / 64)] in client order); a shard without
+ * a survivor becomes an empty shard.
+ *
+ * fhh_retain_plan is the host arithmetic of that call, no device call (like fhh_shard_plan /
+ * fhh_frontier_plan): *n_kept = the survivors, src[k] = the old index of the k-th survivor, increasing.
+ * Either output may be NULL. FHH_E_ARG (nothing written) for n = 0, a NULL keep, n >= 2^32, a byte other than
+ * 0/1, or no survivor: fhh_tree_prune tolerates an all-false mask, but a collection of zero clients has no
+ * layout — the caller resets instead.
+ *
+ * fhh_retain_timing is for diagnostics only (tools/retain_time.py; like fhh_set_expand_grid, not part of what a
+ * server binds): ms[2] = the column and plane gather kernels' time (HIP events) of the last fhh_retain_clients
+ * that ran them on this ctx, bytes[2] = what they read plus wrote. */
+int fhh_retain_clients(fhh_ctx* ctx, const uint8_t* keep, uint64_t n);
+int fhh_retain_plan(const uint8_t* keep, uint64_t n, uint64_t* n_kept, uint32_t* src);
+int fhh_retain_timing(const fhh_ctx* ctx, double* ms, uint64_t* bytes);
 
 /* Frontier expansion of tree_crawl (collect.rs:379-418): evaluates every client's 2d keys
  * one level for every child of every frontier node. *n_children = C. share_planes (may be
