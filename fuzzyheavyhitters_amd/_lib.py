@@ -59,6 +59,7 @@ EXPORTS = [
     "fhh_bincode_request_bytes", "fhh_export_keys_bincode",
     "fhh_frontier_plan", "fhh_tree_init_at", "fhh_frontier_paths",
     "fhh_retain_clients", "fhh_retain_plan", "fhh_retain_timing",
+    "fhh_retain_clients_device", "fhh_retain_plan_device", "fhh_retain_mask_timing",
 ]
 
 
@@ -115,7 +116,7 @@ class FhhSimConfig(ctypes.Structure):
     ]
 
 
-SOURCES = ("fhh_kernels.hip", "fhh_bincode_out.hip", "fhh_retain.hip", "fhh_sketch.hip", "fhh_gc.hip", "fhh_ot.hip",
+SOURCES = ("fhh_kernels.hip", "fhh_bincode_out.hip", "fhh_retain.hip", "fhh_retain_mask.hip", "fhh_sketch.hip", "fhh_gc.hip", "fhh_ot.hip",
            "fhh_loop.hip", "fhh_microbench.hip", "fhh_host.cpp", "fhh_keys_io.cpp", "fhh_retain.cpp",
            "fhh_sim_crawl.cpp", "fhh_sketch_host.cpp",
            "fhh_gcot.cpp", "fhh_gcot_harness.cpp", "fhh_group.cpp", "fhh_comm.cpp", "fhh_base_ot.cpp")
@@ -329,6 +330,9 @@ def lib():
         "fhh_retain_clients": (i, [vp, u8p, u64]),
         "fhh_retain_plan": (i, [u8p, u64, u64p, u32p]),
         "fhh_retain_timing": (i, [vp, P(ctypes.c_double), u64p]),
+        "fhh_retain_clients_device": (i, [vp, vp, u64, u32, u64, u64p]),
+        "fhh_retain_plan_device": (i, [vp, vp, u64, u32, u64, u64p, u32p]),
+        "fhh_retain_mask_timing": (i, [vp, P(ctypes.c_double)]),
         "fhh_tree_crawl": (i, [vp, u64p, u64p]),
         "fhh_tree_crawl_last": (i, [vp, u64p, u64p]),
         "fhh_node_sums_fe": (i, [vp, u64p, u64p]),

@@ -32,6 +32,36 @@ def _keep_bytes(keep) -> np.ndarray:
     return np.ascontiguousarray(a.astype(np.uint8)).reshape(-1)
 
 
+def _device_mask(keep, n, n_rows, row_stride):
+    """(pointer, n, n_rows, row_stride) of a keep mask in device memory: a torch.uint8 tensor [n] or [rows, n] on a
+    GPU, or an integer device pointer with the sizes given. What the C ABI cannot see is refused here: a dtype
+    other than uint8, a CPU tensor, a column stride other than 1, rows that overlap."""
+    if isinstance(keep, (int, np.integer)):
+        if n is None:
+            raise FhhError("keep mask given as a device pointer: n is required")
+        if n_rows > 1 and row_stride is None:
+            raise FhhError("keep mask given as a device pointer with several rows: row_stride is required")
+        return ctypes.c_void_p(int(keep)), int(n), int(n_rows), int(n if row_stride is None else row_stride)
+    if not (hasattr(keep, "data_ptr") and hasattr(keep, "is_cuda")):
+        raise FhhError("keep mask: a torch.uint8 tensor on the GPU or an integer device pointer expected "
+                       "(a host mask goes to retain_clients)")
+    import torch
+    if keep.dtype != torch.uint8:
+        raise FhhError(f"keep mask of dtype {keep.dtype}: torch.uint8 expected")
+    if not keep.is_cuda:
+        raise FhhError("keep mask on the CPU: retain_clients takes host masks")
+    if keep.dim() not in (1, 2):
+        raise FhhError(f"keep mask of shape {tuple(keep.shape)}: [n] or [rows, n] expected")
+    rows, cols = (1, keep.shape[0]) if keep.dim() == 1 else keep.shape
+    if cols > 1 and keep.stride(-1) != 1:
+        raise FhhError("keep mask: the clients of a row must be contiguous (column stride 1)")
+    stride = cols if keep.dim() == 1 or rows == 1 else keep.stride(0)
+    if rows > 1 and stride < cols:
+        raise FhhError("keep mask: row stride below the row length")
+    torch.cuda.synchronize(keep.device)   # the library reads on its own stream: torch's writes must be complete
+    return ctypes.c_void_p(keep.data_ptr()), int(cols), int(rows), int(stride)
+
+
 class KeyCollection:
     """One server's key collection (collect.rs:45-1030) on one GPU, or — with `devices` — one
     collection whose clients are sharded over several GPUs (fhh_create_multi: contiguous ranges
@@ -185,6 +215,32 @@ class KeyCollection:
         src = np.zeros(max(k.size, 1), np.uint32)
         check(lib().fhh_retain_plan(ptr(k) if k.size else None, k.size, ctypes.byref(nk), ptr(src, u32p)))
         return int(nk.value), src[: nk.value].copy()
+
+    def retain_clients_device(self, keep, n=None, n_rows=1, row_stride=None) -> int:
+        """`retain_clients` with the mask in device memory (fhh_retain_clients_device): the mask never crosses to
+        the host. keep: a CUDA/HIP torch.uint8 tensor [n] or [rows, n] (row stride >= n, unit column stride), or an
+        integer device pointer with n / n_rows / row_stride given. A client survives iff its byte is 1 in every
+        row. The tensor's device is synchronised first: the library reads the mask on its own stream. Returns the
+        number of survivors."""
+        p, n, n_rows, row_stride = _device_mask(keep, n, n_rows, row_stride)
+        nk = ctypes.c_uint64()
+        self._chk(lib().fhh_retain_clients_device(self._h, p, n, n_rows, row_stride, ctypes.byref(nk)))
+        return int(nk.value)
+
+    def retain_plan_device(self, keep, n=None, n_rows=1, row_stride=None):
+        """fhh_retain_plan_device (the survivor-list kernels alone, on this collection's device and stream): (n_kept,
+        src) as `retain_plan` gives them, of a mask as `retain_clients_device` takes it."""
+        p, n, n_rows, row_stride = _device_mask(keep, n, n_rows, row_stride)
+        nk = ctypes.c_uint64()
+        src = np.zeros(max(n, 1), np.uint32)
+        self._chk(lib().fhh_retain_plan_device(self._h, p, n, n_rows, row_stride, ctypes.byref(nk), ptr(src, u32p)))
+        return int(nk.value), src[: nk.value].copy()
+
+    def retain_mask_timing(self):
+        """(words + scan ms, emit ms) of the survivor-list kernels' last runs on this collection (HIP events)."""
+        ms = (ctypes.c_double * 2)()
+        self._chk(lib().fhh_retain_mask_timing(self._h, ms))
+        return ms[0], ms[1]
 
     def retain_timing(self):
         """((column ms, plane ms), (column bytes, plane bytes)) of the last retain_clients that ran its kernels."""

@@ -150,6 +150,11 @@ struct fhh_ctx {
     // bytes they read plus wrote (fhh_retain_timing)
     double retain_ms[2] = {0, 0};
     uint64_t retain_bytes[2] = {0, 0};
+    // fhh_retain_clients_device / fhh_retain_plan_device: [record | keep words | prefix counts] of the last mask
+    // scanned here, the rows of a mask that lives on another device, and the survivor-list kernels' time (words +
+    // scan, emit; HIP events), kept from call to call
+    DevBuf keep_scan, keep_stage;
+    double keep_ms[2] = {0, 0};
     DimTable tab[kMaxDims];
 
     Phase phase = Phase::kNoInit;
@@ -347,17 +352,46 @@ struct RetainStage {
     size_t cap[kMaxDims] = {0, 0, 0, 0};
     double ms[2] = {0, 0};
     uint64_t bytes[2] = {0, 0};
+    double emit_ms = -1;          // k_keep_emit's time when the list came from a device mask
 };
+// A keep mask in device memory (fhh_retain_clients_device): n_rows rows of n bytes, row r at keep + r * row_stride,
+// resident on `device`; a client survives iff its byte is 1 in every row.
+struct KeepMask {
+    const uint8_t* keep = nullptr;
+    uint64_t n = 0;
+    uint32_t n_rows = 0;
+    uint64_t row_stride = 0;
+    int device = 0;
+};
+// what keep_scan_run leaves in ctx->keep_scan for the emit kernel (device pointers, valid until its next run)
+struct KeepScan {
+    const uint64_t* words = nullptr;
+    const uint32_t* base = nullptr;
+    uint64_t nw = 0;
+};
+// the argument refusals of the device-mask calls and the pointer check (no kernel, no ctx); fills m
+bool keep_mask_check(const uint8_t* keep_dev, uint64_t n, uint32_t n_rows, uint64_t row_stride, KeepMask& m,
+                     std::string* err);
+// the AND of m's rows on the host, for keys that are staged there; FHH_E_ARG for a byte other than 0/1
+int keep_mask_to_host(const KeepMask& m, std::vector<uint8_t>& keep, std::string* err);
+// k_keep_words + k_keep_scan over clients [first, first + count) of m on ctx's device and stream (the rows copied
+// there first if the mask lives elsewhere), the record read back; returns once the stream has drained
+int keep_scan_run(fhh_ctx* ctx, const KeepMask& m, uint64_t first, uint64_t count, KeepScan& ks, KeepRecord& rec);
+bool keep_record_check(const KeepRecord& rec, std::string* err);   // false for a bad byte or no survivor
 int retain_check_state(fhh_ctx* ctx);   // FHH_E_STATE in the phases fhh_retain_clients refuses (one-GPU ctx)
-// gather the survivors src[0 .. n2) of a one-GPU ctx into `st` (allocated before the first launch; returns once
-// the stream has drained); the ctx is not changed
-int retain_prepare(fhh_ctx* ctx, const uint32_t* src, uint64_t n2, RetainStage& st);
+// gather the n2 survivors of a one-GPU ctx into `st` (allocated before the first launch; returns once the stream
+// has drained); the ctx is not changed. The survivor list is src[0 .. n2) on the host, or (src NULL) the one
+// k_keep_emit writes from `scan`
+int retain_prepare(fhh_ctx* ctx, const uint32_t* src, const KeepScan* scan, uint64_t n2, RetainStage& st);
 void retain_commit(fhh_ctx* ctx, RetainStage& st);   // host only: cannot fail
 // the survivors' records of add_keys-layout host vectors
 void retain_host_keys(const fhh_ctx* ctx, const uint32_t* src, uint64_t n2, RetainStage& st);
 
 // ---- fhh_group.cpp (multi-device ctx) --------------------------------------------------------
 int group_retain_clients(fhh_ctx* g, const uint8_t* keep, uint64_t n);
+int group_retain_clients_device(fhh_ctx* g, const uint8_t* keep_dev, uint64_t n, uint32_t n_rows, uint64_t row_stride,
+                                uint64_t* n_kept);
+fhh_ctx* group_shard0(const fhh_ctx* g);   // the first shard, whatever it holds (its device and stream)
 void group_destroy(fhh_ctx* g);
 int group_reset(fhh_ctx* g);
 int group_set_client_base(fhh_ctx* g, uint64_t base);

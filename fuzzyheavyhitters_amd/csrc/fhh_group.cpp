@@ -566,9 +566,11 @@ int group_tree_prune(fhh_ctx* g, const uint8_t* keep, uint64_t n, bool last) {
 // fhh_retain_clients on a multi-device ctx: each shard retains its own slice of the mask on its own GPU and
 // stream; the shards' ranges become the prefix sums of their survivor counts (no longer whole words: see
 // group_tree_crawl). Every shard gathers into buffers of its own first; they swap only when all have succeeded.
-int group_retain_clients(fhh_ctx* g, const uint8_t* keep, uint64_t n) {
+namespace {
+
+// the states both forms of the call refuse, on every shard before anything else
+int group_retain_check_state(fhh_ctx* g) {
     Group& G = *g->group;
-    const size_t S = G.shards.size();
     if (!G.placed && g->h_n == 0) return g->fail(FHH_E_STATE, "retain_clients: the ctx holds no keys");
     if (G.placed) {
         for (size_t k : G.active()) {
@@ -579,6 +581,55 @@ int group_retain_clients(fhh_ctx* g, const uint8_t* keep, uint64_t n) {
             if (rc) return shard_fail(g, k, rc);
         }
     }
+    return FHH_OK;
+}
+
+// The tail both forms share, on a placed collection: kept[k] = shard k's survivors (somebody leaves, somebody
+// stays), prep(k, s, st) = retain_prepare of a partial shard with the list in the caller's form.
+template <class Prep>
+int group_retain_apply(fhh_ctx* g, const std::vector<uint64_t>& kept, Prep prep) {
+    Group& G = *g->group;
+    const size_t S = G.shards.size();
+    std::vector<std::unique_ptr<RetainStage>> st(S);
+    for (auto& p : st) p.reset(new RetainStage());
+    auto partial = [&](size_t k) { return kept[k] != 0 && kept[k] != G.count[k]; };
+    const int rc = fan_out(g, [&](size_t k, fhh_ctx* s) {
+        if (!partial(k)) return (int)FHH_OK;
+        return prep(k, s, *st[k]);
+    });
+    if (rc) return rc;   // no shard has changed
+    g->retain_ms[0] = g->retain_ms[1] = 0;
+    g->retain_bytes[0] = g->retain_bytes[1] = 0;
+    uint64_t base = 0;
+    for (size_t k = 0; k < S; k++) {
+        fhh_ctx* s = G.shards[k];
+        if (partial(k)) {
+            retain_commit(s, *st[k]);
+            for (int i = 0; i < 2; i++) {
+                g->retain_ms[i] = std::max(g->retain_ms[i], s->retain_ms[i]);
+                g->retain_bytes[i] += s->retain_bytes[i];
+            }
+        } else if (G.count[k] && kept[k] == 0) {
+            (void)fhh_reset(s);   // no survivor: the empty-shard state (the shard takes no part from here on)
+        }
+        G.base[k] = base;
+        G.count[k] = kept[k];
+        base += G.count[k];
+    }
+    // the collection is now a placed one of n' clients, whatever path its keys came by
+    G.appended = false;
+    G.reserved = G.app_n = 0;
+    set_bases(G);
+    return FHH_OK;
+}
+
+}  // namespace
+
+int group_retain_clients(fhh_ctx* g, const uint8_t* keep, uint64_t n) {
+    Group& G = *g->group;
+    const size_t S = G.shards.size();
+    int rc = group_retain_check_state(g);
+    if (rc) return rc;
     std::vector<uint32_t> src;
     std::string why;
     if (!retain_plan(keep, n, src, &why)) return g->fail(FHH_E_ARG, "retain_clients: " + why);
@@ -602,38 +653,71 @@ int group_retain_clients(fhh_ctx* g, const uint8_t* keep, uint64_t n) {
             loc[k].push_back((uint32_t)(i - G.base[k]));
         }
     }
-    std::vector<std::unique_ptr<RetainStage>> st(S);
-    for (auto& p : st) p.reset(new RetainStage());
-    auto partial = [&](size_t k) { return !loc[k].empty() && loc[k].size() != G.count[k]; };
-    const int rc = fan_out(g, [&](size_t k, fhh_ctx* s) {
-        if (!partial(k)) return (int)FHH_OK;
-        return retain_prepare(s, loc[k].data(), loc[k].size(), *st[k]);
+    std::vector<uint64_t> kept(S);
+    for (size_t k = 0; k < S; k++) kept[k] = loc[k].size();
+    return group_retain_apply(g, kept, [&](size_t k, fhh_ctx* s, RetainStage& st) {
+        return retain_prepare(s, loc[k].data(), nullptr, loc[k].size(), st);
     });
-    if (rc) return rc;   // no shard has changed
-    g->retain_ms[0] = g->retain_ms[1] = 0;
-    g->retain_bytes[0] = g->retain_bytes[1] = 0;
-    uint64_t base = 0;
-    for (size_t k = 0; k < S; k++) {
-        fhh_ctx* s = G.shards[k];
-        if (partial(k)) {
-            retain_commit(s, *st[k]);
-            for (int i = 0; i < 2; i++) {
-                g->retain_ms[i] = std::max(g->retain_ms[i], s->retain_ms[i]);
-                g->retain_bytes[i] += s->retain_bytes[i];
-            }
-        } else if (G.count[k] && loc[k].empty()) {
-            (void)fhh_reset(s);   // no survivor: the empty-shard state (the shard takes no part from here on)
-        }
-        G.base[k] = base;
-        G.count[k] = loc[k].size();
-        base += G.count[k];
+}
+
+// fhh_retain_clients_device on a multi-device ctx, in three phases: every shard scans its slice of the mask on its
+// own GPU (the rows copied there first when the mask lives on another device); the host reads the S records and
+// decides for the collection (the lowest bad index, no survivor overall, nobody leaves); then the partial shards
+// emit, gather and commit as in group_retain_clients.
+int group_retain_clients_device(fhh_ctx* g, const uint8_t* keep_dev, uint64_t n, uint32_t n_rows, uint64_t row_stride,
+                                uint64_t* n_kept) {
+    Group& G = *g->group;
+    const size_t S = G.shards.size();
+    int rc = group_retain_check_state(g);
+    if (rc) return rc;
+    uint64_t have = 0;
+    group_num_clients(g, &have);
+    if (n != have)
+        return g->fail(FHH_E_ARG, "retain_clients: keep.len() " + std::to_string(n) + " != " + std::to_string(have) +
+                                      " clients");
+    KeepMask m;
+    std::string why;
+    if (!keep_mask_check(keep_dev, n, n_rows, row_stride, m, &why)) return g->fail(FHH_E_ARG, "retain_clients: " + why);
+    if (!G.placed) {   // still staged on the collection by fhh_add_keys: the mask joins the keys on the host
+        std::vector<uint8_t> keep;
+        rc = keep_mask_to_host(m, keep, &why);
+        if (rc) return g->fail(rc, "retain_clients: " + why);
+        rc = group_retain_clients(g, keep.data(), n);
+        if (rc == FHH_OK && n_kept) *n_kept = g->h_n;
+        return rc;
     }
-    // the collection is now a placed one of n' clients, whatever path its keys came by
-    G.appended = false;
-    G.reserved = G.app_n = 0;
-    set_bases(G);
+    // 1. words + scan of every shard's slice
+    std::vector<KeepScan> ks(S);
+    std::vector<KeepRecord> rec(S, KeepRecord{0, kKeepNoBad});
+    rc = fan_out(g, [&](size_t k, fhh_ctx* s) { return keep_scan_run(s, m, G.base[k], G.count[k], ks[k], rec[k]); });
+    if (rc) return rc;
+    // 2. the S records: one verdict for the collection
+    KeepRecord all{0, kKeepNoBad};
+    std::vector<uint64_t> kept(S, 0);
+    g->keep_ms[0] = g->keep_ms[1] = 0;
+    for (size_t k : G.active()) {
+        if (rec[k].bad != kKeepNoBad) all.bad = std::min(all.bad, rec[k].bad + (G.base[k] << 8));
+        kept[k] = rec[k].n_kept;
+        all.n_kept += kept[k];
+        g->keep_ms[0] = std::max(g->keep_ms[0], G.shards[k]->keep_ms[0]);
+    }
+    if (!keep_record_check(all, &why)) return g->fail(FHH_E_ARG, "retain_clients: " + why);
+    if (all.n_kept != n) {   // else nobody leaves: no shard's buffers are touched
+        // 3. emit, gather, commit
+        std::vector<size_t> partial;
+        for (size_t k = 0; k < S; k++)
+            if (kept[k] && kept[k] != G.count[k]) partial.push_back(k);
+        rc = group_retain_apply(g, kept, [&](size_t k, fhh_ctx* s, RetainStage& st) {
+            return retain_prepare(s, nullptr, &ks[k], kept[k], st);
+        });
+        if (rc) return rc;
+        for (size_t k : partial) g->keep_ms[1] = std::max(g->keep_ms[1], G.shards[k]->keep_ms[1]);
+    }
+    if (n_kept) *n_kept = all.n_kept;
     return FHH_OK;
 }
+
+fhh_ctx* group_shard0(const fhh_ctx* g) { return g->group->shards[0]; }
 
 fhh_ctx* group_lead(const fhh_ctx* g) {
     const Group& G = *g->group;

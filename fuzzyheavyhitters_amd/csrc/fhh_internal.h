@@ -373,6 +373,19 @@ hipError_t launch_retain_cols(const uint4* src, uint4* dst, const uint32_t* idx,
                               uint64_t npad, uint64_t npad2, uint32_t n2, hipStream_t stream);
 hipError_t launch_retain_planes(const uint64_t* src, uint64_t* dst, const uint32_t* idx, const uint32_t* rows,
                                 uint64_t n_rows, uint64_t nw, uint64_t nw2, uint32_t n2, hipStream_t stream);
+// fhh_retain_mask.hip (fhh_retain_clients_device): that idx list from a keep mask in device memory, n_rows rows of
+// n < 2^32 bytes at keep + r * row_stride, a client kept iff its byte is 1 in every row. launch_keep_scan leaves
+// the keep words [nw], their exclusive prefix counts base [nw] (nw = ceil(n / 64)) and the record;
+// launch_keep_emit writes idx[0 .. n_kept) from them.
+struct KeepRecord {
+    uint64_t n_kept;   // survivors
+    uint64_t bad;      // (client index << 8 | byte) of the lowest client with a byte other than 0/1; ~0: none
+};
+constexpr uint64_t kKeepNoBad = ~0ull;
+hipError_t launch_keep_scan(const uint8_t* keep, uint64_t n, uint32_t n_rows, uint64_t row_stride, uint64_t* words,
+                            uint32_t* base, KeepRecord* rec, hipStream_t stream);
+hipError_t launch_keep_emit(const uint64_t* words, const uint32_t* base, uint64_t nw, uint32_t* idx,
+                            hipStream_t stream);
 // fhh_bincode_out.hip: clients [src_first, src_first + m) of the layout as clients [i0, i0 + m) of an export of
 // `count` clients in requests of B (bincode_emit.h); byte g of the export goes to stg[g - org], org % 4 == 0 and
 // org <= be_slice_begin(i0), stg holding be_slice_end(i0, m) - org bytes

@@ -246,6 +246,26 @@ def apply_sketch_results(c0, c1, ok) -> int:
     return int(keep.sum())
 
 
+def apply_sketch_results_device(c0, c1, batch, level: int = 0, n_levels: int = 1) -> int:
+    """`apply_sketch_results` on verdicts that stay on the GPU: rows [level, level + n_levels) of `batch.ok` (a
+    DeviceSketchBatch; a DeviceSketchBatch255 has the one row of the last level) go to both collections as they
+    lie in device memory (KeyCollection.retain_clients_device), and a client survives iff every row accepts it.
+    The mask is never copied to the host. Returns the number of survivors."""
+    ok = batch.ok
+    if ok.dim() == 1:
+        if level != 0 or n_levels != 1:
+            raise FhhError("apply_sketch_results_device: this batch has the single row of the last level")
+    else:
+        if n_levels < 1 or level < 0 or level + n_levels > ok.shape[0]:
+            raise FhhError(f"apply_sketch_results_device: levels [{level}, {level + n_levels}) outside the batch's "
+                           f"{ok.shape[0]} rows")
+        ok = ok[level:level + n_levels]
+    kept = c0.retain_clients_device(ok)
+    if c1.retain_clients_device(ok) != kept:
+        raise FhhError("apply_sketch_results_device: the two collections kept different clients")
+    return kept
+
+
 # ---- U = FieldElm: the last level (sketch_at_last, MulState<FieldElm>) -----------------------
 _P255_LIMBS = np.array([(FE255_P >> (32 * k)) & 0xFFFFFFFF for k in range(8)], np.int64)
 

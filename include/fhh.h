@@ -270,6 +270,48 @@ int fhh_retain_clients(fhh_ctx* ctx, const uint8_t* keep, uint64_t n);
 int fhh_retain_plan(const uint8_t* keep, uint64_t n, uint64_t* n_kept, uint32_t* src);
 int fhh_retain_timing(const fhh_ctx* ctx, double* ms, uint64_t* bytes);
 
+/* fhh_retain_clients with the mask where the sketch verification left it: keep_dev is DEVICE memory holding n_rows
+ * rows of n bytes, row r at keep_dev + r * row_stride — the layout of fhh_sketch_batch.ok_dev with row_stride =
+ * n_keys, and of fhh_sketch_batch255.ok_dev with one row. Client i survives iff byte i is 1 in every row (the AND
+ * of the levels' verdicts); the bytes between n and row_stride belong to nobody and are never read. n_rows = 0 is
+ * FHH_E_ARG; row_stride is ignored when n_rows = 1 and must be >= n otherwise. *n_kept (may be NULL) receives n'.
+ * The mask must be complete when the call is made: the library reads it on the ctx's own stream, as everywhere
+ * else in this ABI, and the call is synchronous like fhh_retain_clients.
+ * The result is defined as that of fhh_retain_clients(ctx, m, n) with m[i] = AND_r keep[r][i]: the allowed states,
+ * the unchanged fields and the multi-device semantics are the ones above, and every refusal, and FHH_E_NOMEM,
+ * leaves the ctx exactly as it was. Refused beyond the host call's refusals (FHH_E_ARG): a NULL keep_dev; a pointer
+ * that hipPointerGetAttributes does not report as device or managed memory (a host pointer is refused before any
+ * kernel could read it, and the query's sticky error is cleared), or whose rows run past the end of its allocation;
+ * a byte other than 0/1 in any row inside [0, n) (the message names the lowest such client index and its value);
+ * no survivor after the AND, also when every row has one. n is checked against fhh_num_clients before any device
+ * work.
+ * Neither the mask nor the survivor list crosses to the host: three kernels make the list on the GPU (a wave per
+ * 64-client word ANDs the rows and ballots the keep word; one workgroup prefix-sums the words' counts; a wave per
+ * word writes its survivors' indices), and between the second and the third the host reads one 16-byte record
+ * (n' and the lowest bad byte) — it needs n' to size the destinations and refuses before anything is allocated.
+ * A mask of all ones returns FHH_OK with *n_kept = n and leaves the collection's buffers untouched; unlike the
+ * host call, counting it does touch the device (the first two kernels and the record).
+ * A mask on another device than the ctx's (or a shard's) is first copied, [0, n) of each row, into a buffer the
+ * ctx owns, so the kernels read local memory only; a mask on the ctx's own device is read in place. With keys still
+ * staged by fhh_add_keys the keys are on the host anyway: the rows are copied there, ANDed, and the host call runs.
+ * On a multi-device ctx every shard scans its own slice on its own GPU, the host reads the shards' records and
+ * decides once for the collection, then the shards that lose some but not all of their clients gather.
+ *
+ * fhh_retain_plan_device is that device arithmetic alone, for diagnostics and tests (like fhh_retain_timing, not
+ * something a server binds): src[k] (HOST memory, up to n entries) = the old index of the k-th survivor and *n_kept
+ * = n'; either may be NULL; nothing is written on a refusal. It refuses what fhh_retain_plan refuses and the masks
+ * above, works on any ctx with or without keys (it needs only the ctx's device and stream; a multi-device ctx
+ * lends its first shard's) and ignores fhh_num_clients.
+ *
+ * fhh_retain_mask_timing, diagnostics too: ms[0] = the words + scan kernels' time (HIP events) of the last device
+ * mask scanned on this ctx, ms[1] = the emit kernel's of the last list written (a multi-device ctx: the slowest
+ * shard's). fhh_retain_timing keeps its meaning, the two gather kernels. */
+int fhh_retain_clients_device(fhh_ctx* ctx, const uint8_t* keep_dev, uint64_t n, uint32_t n_rows, uint64_t row_stride,
+                              uint64_t* n_kept);
+int fhh_retain_plan_device(fhh_ctx* ctx, const uint8_t* keep_dev, uint64_t n, uint32_t n_rows, uint64_t row_stride,
+                           uint64_t* n_kept, uint32_t* src);
+int fhh_retain_mask_timing(const fhh_ctx* ctx, double* ms);
+
 /* Frontier expansion of tree_crawl (collect.rs:379-418): evaluates every client's 2d keys
  * one level for every child of every frontier node. *n_children = C. share_planes (may be
  * NULL) receives [C][2d][nw] u64 — the GC input of collect.rs:415-418.

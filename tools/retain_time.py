@@ -15,7 +15,12 @@ the clients, then --drop[1] (50 %) of the rest, the same mask on both servers. P
                 gather's rate
 
 and checks once per step (round 0) that the exported states of the retained pair equal route (a)'s; the run exits
-non-zero if they differ. Medians and raw rounds go to --out as JSON."""
+non-zero if they differ. Medians and raw rounds go to --out as JSON.
+
+--device-mask adds, under the key "device_mask", the same two steps with the mask starting in device memory, as the
+sketch verification leaves it: ok.cpu() -> retain_clients on both servers against retain_clients_device on both
+(fhh_retain_clients_device), on twin pairs at the same frontier, with the survivor-list kernels' own time
+(profiles/retain/device_mask.json)."""
 import argparse
 import json
 import os
@@ -39,6 +44,9 @@ def main():
     ap.add_argument("--seed", type=lambda s: int(s, 0), default=0x5EED)
     ap.add_argument("--drop", type=float, nargs="+", default=[0.01, 0.5])
     ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--device-mask", action="store_true",
+                    help="also time a mask that starts on the GPU: ok.cpu() -> retain_clients against retain_clients_device")
+    ap.add_argument("--mask-rounds", type=int, default=5, help="timed rounds of --device-mask (after one warm-up)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if not 0 < a.depth < a.L:
@@ -135,6 +143,62 @@ def main():
     for st in steps:
         st["memcpy_copied_bytes"] = st["column_bytes"] // 2
         st["memcpy_ms_rounds"] = memcpy_ms(st["memcpy_copied_bytes"])
+    def device_mask():
+        """--device-mask: the mask starts on the GPU (where the sketch verification leaves `ok`). Route (a), the only
+        one before retain_clients_device: ok.cpu() -> retain_clients on both servers. Route (b): retain_clients_device
+        on both. Twin pairs at the same frontier, the same steps; the wall time is taken between two device
+        synchronisations; round 0 warms up and checks that the two pairs' exported states are equal."""
+        out = [{"drop": f, "host_mask_s": [], "device_mask_s": [], "words_scan_ms": [], "emit_ms": []} for f in a.drop]
+        for r in range(a.mask_rounds + 1):
+            pa, pb = build_pair(), build_pair()
+            for k, keep in enumerate(keeps):
+                st = out[k]
+                ok = torch.from_numpy(keep).cuda()
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                host = ok.cpu().numpy()
+                for c in pa:
+                    c.retain_clients(host)
+                torch.cuda.synchronize()
+                sa = time.perf_counter() - t0
+                t0 = time.perf_counter()
+                kept = [c.retain_clients_device(ok) for c in pb]
+                torch.cuda.synchronize()
+                sb = time.perf_counter() - t0
+                tm = [c.retain_mask_timing() for c in pb]
+                if kept != [int(keep.sum())] * 2:
+                    sys.exit(f"retain_time: device mask step {k}: {kept} survivors, {int(keep.sum())} expected")
+                if r:
+                    st["host_mask_s"].append(sa)
+                    st["device_mask_s"].append(sb)
+                    st["words_scan_ms"].append(sum(t[0] for t in tm))
+                    st["emit_ms"].append(sum(t[1] for t in tm))
+                    continue
+                st["n_before"], st["n_after"] = int(keep.size), int(keep.sum())
+                for s_idx, (x, y) in enumerate(zip(pa, pb)):
+                    for u, v, name in zip(x.export_states(), y.export_states(), ("seed", "t", "y")):
+                        if u.shape != v.shape or not np.array_equal(u, v):
+                            sys.exit(f"retain_time: device mask step {k} server {s_idx}: the {name} states of the two "
+                                     "routes differ")
+                st["states_equal"] = True
+            del pa, pb
+        steps_out = []
+        for st in out:
+            ha, hb = statistics.median(st["host_mask_s"]), statistics.median(st["device_mask_s"])
+            steps_out.append({
+                "drop": st["drop"], "n_before": st["n_before"], "n_after": st["n_after"], "states_equal": st["states_equal"],
+                "host_mask_s_median": ha, "host_mask_s_rounds": st["host_mask_s"],
+                "device_mask_s_median": hb, "device_mask_s_rounds": st["device_mask_s"],
+                "host_over_device": ha / hb,
+                "words_scan_ms_median": statistics.median(st["words_scan_ms"]), "words_scan_ms_rounds": st["words_scan_ms"],
+                "emit_ms_median": statistics.median(st["emit_ms"]), "emit_ms_rounds": st["emit_ms"],
+            })
+        return {"rounds": a.mask_rounds, "warmup_rounds": 1,
+                "timed": "host_mask_s: ok.cpu() -> retain_clients on both servers; device_mask_s: retain_clients_device "
+                         "on both servers; host clock between two device synchronisations, each round on fresh pairs; "
+                         "words_scan_ms / emit_ms: the survivor-list kernels of both servers, HIP events",
+                "steps": steps_out}
+
     res = {"n": a.n, "L": a.L, "d": a.d, "depth": a.depth, "threshold": a.threshold, "frontier_nodes": len(mid),
            "rounds": a.rounds, "warmup_rounds": 1, "servers": 2,
            "timed": "retain_s / route_a_s: host clock around both servers' synchronous calls; *_ms: HIP events",
@@ -153,6 +217,8 @@ def main():
             "column_gather_over_memcpy": cols / mc,
             "route_a_s": st["route_a_s"], "route_a_over_retain": st["route_a_s"] / statistics.median(st["retain_s"]),
         })
+    if a.device_mask:
+        res["device_mask"] = device_mask()
     print(json.dumps(res))
     if a.out:
         with open(a.out, "w") as f:
