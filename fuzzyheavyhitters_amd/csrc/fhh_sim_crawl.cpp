@@ -451,19 +451,29 @@ int loop_entry_cap(Loop& B, uint32_t need, uint32_t la, uint32_t& out) {
     return FHH_OK;
 }
 
-// (re)size the loop buffers; preserve what a resumed prune of `level` still reads
+// (re)size the loop buffers; preserve what a resumed prune of `level` still reads, and with keep_live (the dims'
+// n_live) the live lists `level` was expanded from: the last level's, which loop_readback hands to the engine
 int loop_resize(fhh_ctx* c0, LoopBuffers& B, uint32_t E_cap, uint32_t F_cap, uint32_t levels, uint32_t level,
-                bool preserve, uint32_t keep_nodes, uint32_t keep_children, uint32_t per) {
+                bool preserve, uint32_t keep_nodes, uint32_t keep_children, uint32_t per,
+                const uint32_t* keep_live = nullptr) {
     const uint32_t d = c0->d;
     const size_t C_new = (size_t)F_cap << d;
     HIP_TRY(c0, hipStreamSynchronize(c0->stream));
     for (int b = 0; b < 2; b++) {
+        const int keep_par = level & 1;
         DevBuf nl;
         HIP_TRY(c0, nl.ensure((size_t)d * E_cap * 4));
+        if (preserve && b == keep_par && keep_live) {
+            for (uint32_t j = 0; j < d; j++)
+                if (keep_live[j])
+                    HIP_TRY(c0, hipMemcpyAsync(nl.as<uint32_t>() + (size_t)j * E_cap,
+                                               B.live[b].as<uint32_t>() + (size_t)j * B.E_cap, (size_t)keep_live[j] * 4,
+                                               hipMemcpyDeviceToDevice, c0->stream));
+            HIP_TRY(c0, hipStreamSynchronize(c0->stream));
+        }
         B.live[b].swap(nl);
         DevBuf np;
         HIP_TRY(c0, np.ensure((size_t)F_cap * d * 4));
-        const int keep_par = level & 1;
         if (preserve && b == keep_par && keep_nodes) {
             // stream-ordered (the engine streams do not wait for the null stream), and finished
             // before the old buffer is released
@@ -994,8 +1004,11 @@ int loop_grow(Loop& S, const LoopCtl* h, uint32_t batch_end) {
     const uint32_t d = S.d;
     const uint32_t la = h->abort_level;
     const bool la_last = la + 1 == S.levels;
-    uint32_t nE = 0;
-    int rc = loop_entry_cap(S, std::max<uint32_t>(h->need_entries, 1), la, nE);
+    // an abort at the last level lacks room for the final nodes only: nothing is expanded after it, and the
+    // tables of parity la & 1 and the live lists of that parity are the frontier the crawl leaves to the engine
+    // (loop_readback), so the tables stay as they are and the lists are carried over
+    uint32_t nE = S.E_cap;
+    int rc = la_last ? FHH_OK : loop_entry_cap(S, std::max<uint32_t>(h->need_entries, 1), la, nE);
     if (rc) return rc;
     const uint32_t nF = std::max(S.F_cap, next_pow2(std::max<uint32_t>(h->need_nodes, 1)) * 2);
     const uint32_t la_per = S.cfg->mode == 0 ? 1 : (la_last ? 16 : 4);
@@ -1006,19 +1019,19 @@ int loop_grow(Loop& S, const LoopCtl* h, uint32_t batch_end) {
     // the tables of parity la & 1 are rewritten by level la + 1: released first, so the
     // peak while the preserved ones are copied is one old table, not all of them
     for (fhh_ctx* c : S.cs)
-        for (uint32_t j = 0; j < d; j++) table_release(c->tab[j], la & 1);
+        for (uint32_t j = 0; j < d && !la_last; j++) table_release(c->tab[j], la & 1);
     for (fhh_ctx* c : S.cs)
-        for (uint32_t j = 0; j < d; j++) {
+        for (uint32_t j = 0; j < d && !la_last; j++) {
             // child tables of level la (parity 1 - la&1) hold 2 * n_live(la) entries
             rc = table_grow(c, c->tab[j], 1 - (la & 1), nE, 2 * (size_t)h->n_live[j]);
             if (rc) return rc;
         }
     for (fhh_ctx* c : S.cs)
-        for (uint32_t j = 0; j < d; j++) {
+        for (uint32_t j = 0; j < d && !la_last; j++) {
             rc = table_grow(c, c->tab[j], la & 1, nE, 0);
             if (rc) return rc;
         }
-    rc = loop_resize(c0, S, nE, nF, S.levels, la, true, h->F, h->C, la_per);
+    rc = loop_resize(c0, S, nE, nF, S.levels, la, true, h->F, h->C, la_per, la_last ? h->n_live : nullptr);
     if (rc) return rc;
     const uint32_t zero = 0;
     HIP_TRY(c0, hipMemcpy(S.ctl.p, &zero, 4, hipMemcpyHostToDevice));   // abort = 0
