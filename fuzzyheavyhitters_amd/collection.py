@@ -330,7 +330,9 @@ class KeyCollection:
     def node_sums_fe_device(self, vals_dev, ld: int, C: int, fmt: int = 0) -> np.ndarray:
         """collect.rs:487-501 on OT outputs already in device memory (no host round trip):
         vals_dev = one device pointer (int) per shard, rows [C][ld] (C = the pending crawl's
-        children); fmt FHH_VALS_FE_U64 / FHH_VALS_FE_BLOCK. Returns canonical FE sums [C]."""
+        children; ld = the row pitch in values, at least the shard's client count, 0 = "this
+        ctx's n": each shard's own client count); fmt FHH_VALS_FE_U64 / FHH_VALS_FE_BLOCK.
+        Returns canonical FE sums [C]."""
         ptrs = (ctypes.c_void_p * len(vals_dev))(*[int(p) for p in vals_dev])
         out = np.zeros(max(C, 1), np.uint64)
         self._chk(lib().fhh_node_sums_fe_device(self._h, ptrs, ld, fmt, ptr(out, u64p)))
@@ -338,7 +340,8 @@ class KeyCollection:
 
     def node_sums_fe255_device(self, vals_dev, ld: int, C: int, fmt: int = 3):
         """collect.rs:891-905 on device-resident FieldElm OT outputs (FHH_VALS_FE255_LIMBS /
-        FHH_VALS_FE255_BLOCKPAIR) -> (unreduced ints, canonical ints)."""
+        FHH_VALS_FE255_BLOCKPAIR), one device pointer per shard, rows [C][ld] with ld as in
+        `node_sums_fe_device` (0 = "this ctx's n") -> (unreduced ints, canonical ints)."""
         ptrs = (ctypes.c_void_p * len(vals_dev))(*[int(p) for p in vals_dev])
         unr = np.zeros((max(C, 1), 10), np.uint32)
         can = np.zeros((max(C, 1), 8), np.uint32)
