@@ -43,6 +43,7 @@ EXPORTS = [
     "fhh_get_stats", "fhh_reset_stats", "fhh_set_timing", "fhh_device_info", "fhh_microbench", "fhh_microbench_gather", "fhh_microbench_hybrid", "fhh_sketch_set_impl", "fhh_sketch_plan",
     "fhh_debug_launch_gaps",
     "fhh_set_variant", "fhh_variant_info", "fhh_set_expand_grid", "fhh_set_table_row_major", "fhh_expand_layout",
+    "fhh_set_protocol_grid", "fhh_protocol_grid",
     "fhh_rccl_load", "fhh_comm_unique_id", "fhh_comm_create", "fhh_comm_destroy", "fhh_comm_allreduce_u64",
     "fhh_comm_info", "fhh_comm_create_hosted", "fhh_comm_last_error",
     "fhh_sketch_at_fe", "fhh_mul_cor_share_fe", "fhh_mul_cor_fe", "fhh_mul_out_share_fe", "fhh_mul_verify_fe",
@@ -365,6 +366,8 @@ def lib():
         "fhh_set_expand_grid": (i, [vp, i]),
         "fhh_set_table_row_major": (i, [vp, i]),
         "fhh_expand_layout": (i, [i, i, u32, u32p, u32, u32p, u32p, u64p]),
+        "fhh_set_protocol_grid": (i, [vp, i]),
+        "fhh_protocol_grid": (i, [vp, i, u64, P(i)]),
         "fhh_rccl_load": (i, [ctypes.c_char_p]),
         "fhh_comm_unique_id": (i, [u8p]),
         "fhh_comm_create": (i, [P(vp), i, i, u8p, i]),

@@ -412,6 +412,17 @@ class KeyCollection:
         instead of the occupancy-derived grid. `set_variant` drops the override: call it first."""
         self._chk(lib().fhh_set_expand_grid(self._h, blocks))
 
+    def set_protocol_grid(self, blocks: int):
+        """Test / diagnostic: cap the grid of every GC / OT launch that sizes itself from the CU count at
+        `blocks` workgroups (0: the device rule again). Outputs do not depend on it."""
+        self._chk(lib().fhh_set_protocol_grid(self._h, blocks))
+
+    def protocol_grid(self, family: int, need: int) -> int:
+        """Test / diagnostic: the grid the launchers of `family` (FHH_GRID_*) use for `need` workgroups."""
+        grid = ctypes.c_int(0)
+        self._chk(lib().fhh_protocol_grid(self._h, family, need, ctypes.byref(grid)))
+        return grid.value
+
     def set_table_row_major(self, on: bool):
         """Tests / diagnostics: the level loop and gc.table_cot run the garbled tables of b = 3, 4 bits (d = 2) on
         the row-major labels (the transpose pass + the row-major kernels) instead of the default tile-major

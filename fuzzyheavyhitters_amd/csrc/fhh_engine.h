@@ -130,6 +130,9 @@ struct fhh_ctx {
     // fhh_set_table_row_major: 1 = b = 3, 4 tables of the level loop and fhh_gt_cot*_host on k_ot_rows_out's
     // row-major labels; 0 (default, profiles/gt_tm_wide/) = the tile-major kernels
     int table_row_major = 0;
+    // fhh_set_protocol_grid: >= 1 caps the grid of every GC / OT launch sized by protocol_grid (fhh_internal.h)
+    // at that many workgroups; 0 (default) = the device rule. Tests and diagnostics only
+    int protocol_grid = 0;
     uint32_t loop_cap_hint = 0;   // device loop: capacity the previous crawl grew to
     DevBuf work_counter;          // dynamic item distribution
     uint32_t expand_seq = 0;      // k_expand launches on work_counter (its counter slot alternates)

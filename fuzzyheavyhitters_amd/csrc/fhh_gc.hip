@@ -1291,33 +1291,19 @@ __global__ __launch_bounds__(kGcThreads) void k_gt_eval_tm(GcArgs a) {
 }
 
 // The launch grid of the kernels that fill the 128 KiB of tables once per workgroup and stride over their work:
-// `need` workgroups, at most per_cu for each CU of the current device, at least one
-static hipError_t gc_grid(uint64_t need, uint32_t per_cu, int* grid) {
-    int dev = 0, cus = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return e;
-    e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    if (e != hipSuccess) return e;
-    const uint64_t cap = (uint64_t)cus * per_cu;
-    *grid = (int)(need < cap ? (need ? need : 1) : cap);
-    return hipSuccess;
-}
-
+// protocol_grid (fhh_internal.h)
 template <int B>
-static hipError_t gt_launch(const GcArgs& a, bool garble, hipStream_t stream) {
-    int grid = 0;
+static hipError_t gt_launch(const GcArgs& a, bool garble, hipStream_t stream, int grid_cap) {
     if (a.lab_tm) {   // r06: one wave per 512-test tile, one 160 KiB workgroup per CU
         const uint64_t tiles = a.G * ((B > kGtTmPadBits ? a.nw + 7 : a.nw) / 8);
-        const hipError_t e = gc_grid((tiles + kGtWaves - 1) / kGtWaves, 1, &grid);
-        if (e != hipSuccess) return e;
+        const int grid = protocol_grid((tiles + kGtWaves - 1) / kGtWaves, kGridGtTm, grid_cap);
         if (garble && a.ring32) hipLaunchKernelGGL((k_gt_garble_tm<B, true>), dim3(grid), dim3(kGcThreads), 0, stream, a);
         else if (garble) hipLaunchKernelGGL((k_gt_garble_tm<B, false>), dim3(grid), dim3(kGcThreads), 0, stream, a);
         else hipLaunchKernelGGL(k_gt_eval_tm<B>, dim3(grid), dim3(kGcThreads), 0, stream, a);
         return hipGetLastError();
     }
     if constexpr (B > kGtTmPadBits) {   // the row-major labels (b = 3, 4), shares in FE or Z_2^32
-        const hipError_t e = gc_grid((a.G * a.N + kGcThreads - 1) / kGcThreads, 8, &grid);
-        if (e != hipSuccess) return e;
+        const int grid = protocol_grid((a.G * a.N + kGcThreads - 1) / kGcThreads, kGridGtRows, grid_cap);
         if (garble && a.ring32) hipLaunchKernelGGL((k_gt_garble<B, true>), dim3(grid), dim3(kGcThreads), 0, stream, a);
         else if (garble) hipLaunchKernelGGL((k_gt_garble<B, false>), dim3(grid), dim3(kGcThreads), 0, stream, a);
         else if (a.ring32) hipLaunchKernelGGL((k_gt_eval<B, true>), dim3(grid), dim3(kGcThreads), 0, stream, a);
@@ -1327,7 +1313,7 @@ static hipError_t gt_launch(const GcArgs& a, bool garble, hipStream_t stream) {
     return hipErrorInvalidValue;   // no row-major table at b <= 2 (gt_dispatch)
 }
 
-static hipError_t gt_dispatch(const GcArgs& a, bool garble, hipStream_t stream) {
+static hipError_t gt_dispatch(const GcArgs& a, bool garble, hipStream_t stream, int grid_cap) {
     if (a.G * a.N == 0) return hipSuccess;
     if (!a.gt_msgs || (!(garble ? a.sh_gb : a.sh_ev) && !(a.lab_tm && a.node_partials)) || !a.ev_labels)
         return hipErrorInvalidValue;
@@ -1338,26 +1324,28 @@ static hipError_t gt_dispatch(const GcArgs& a, bool garble, hipStream_t stream) 
     // at b <= 2 tile-major for all its callers (tests/host/gt_plan_host_test.cpp)
     if (!a.lab_tm && a.bits <= (uint32_t)kGtTmPadBits) return hipErrorInvalidValue;
     switch (a.bits) {
-        case 1: return gt_launch<1>(a, garble, stream);
-        case 2: return gt_launch<2>(a, garble, stream);
-        case 3: return gt_launch<3>(a, garble, stream);
-        case 4: return gt_launch<4>(a, garble, stream);
+        case 1: return gt_launch<1>(a, garble, stream, grid_cap);
+        case 2: return gt_launch<2>(a, garble, stream, grid_cap);
+        case 3: return gt_launch<3>(a, garble, stream, grid_cap);
+        case 4: return gt_launch<4>(a, garble, stream, grid_cap);
         default: return hipErrorInvalidValue;
     }
 }
 
-hipError_t launch_gt_garble(const GcArgs& a, hipStream_t stream) { return gt_dispatch(a, true, stream); }
+hipError_t launch_gt_garble(const GcArgs& a, hipStream_t stream, int grid_cap) {
+    return gt_dispatch(a, true, stream, grid_cap);
+}
 
-hipError_t launch_gt_eval(const GcArgs& a, hipStream_t stream) { return gt_dispatch(a, false, stream); }
+hipError_t launch_gt_eval(const GcArgs& a, hipStream_t stream, int grid_cap) {
+    return gt_dispatch(a, false, stream, grid_cap);
+}
 
 template <int B>
-static hipError_t gc_launch(const GcArgs& a, bool garble, hipStream_t stream) {
+static hipError_t gc_launch(const GcArgs& a, bool garble, hipStream_t stream, int grid_cap) {
     // 8 workgroups per CU (one resident per CU, each filling its tables once, measured -5.6 % for
     // evaluate at configs[1] but +3.2 % for evaluate and +0.7 % for the whole GC + OT crawl at 1M
     // clients, alternated twice; r03)
-    int grid = 0;
-    const hipError_t e = gc_grid((a.G * a.N + kGcThreads - 1) / kGcThreads, 8, &grid);
-    if (e != hipSuccess) return e;
+    const int grid = protocol_grid((a.G * a.N + kGcThreads - 1) / kGcThreads, kGridGc, grid_cap);
     if (garble && a.ev_ot) hipLaunchKernelGGL(k_gc_garble_cot<B>, dim3(grid), dim3(kGcThreads), 0, stream, a);
     else if (garble) hipLaunchKernelGGL(k_gc_garble<B>, dim3(grid), dim3(kGcThreads), 0, stream, a);
     else if (a.ev_ot) hipLaunchKernelGGL((k_gc_eval<B, true>), dim3(grid), dim3(kGcThreads), 0, stream, a);
@@ -1365,23 +1353,27 @@ static hipError_t gc_launch(const GcArgs& a, bool garble, hipStream_t stream) {
     return hipGetLastError();
 }
 
-static hipError_t gc_dispatch(const GcArgs& a, bool garble, hipStream_t stream) {
+static hipError_t gc_dispatch(const GcArgs& a, bool garble, hipStream_t stream, int grid_cap) {
     if (a.G * a.N == 0) return hipSuccess;
     switch (a.bits) {
-        case 1: return gc_launch<1>(a, garble, stream);
-        case 2: return gc_launch<2>(a, garble, stream);
-        case 3: return gc_launch<3>(a, garble, stream);
-        case 4: return gc_launch<4>(a, garble, stream);
-        case 5: return gc_launch<5>(a, garble, stream);
-        case 6: return gc_launch<6>(a, garble, stream);
-        case 7: return gc_launch<7>(a, garble, stream);
-        case 8: return gc_launch<8>(a, garble, stream);
+        case 1: return gc_launch<1>(a, garble, stream, grid_cap);
+        case 2: return gc_launch<2>(a, garble, stream, grid_cap);
+        case 3: return gc_launch<3>(a, garble, stream, grid_cap);
+        case 4: return gc_launch<4>(a, garble, stream, grid_cap);
+        case 5: return gc_launch<5>(a, garble, stream, grid_cap);
+        case 6: return gc_launch<6>(a, garble, stream, grid_cap);
+        case 7: return gc_launch<7>(a, garble, stream, grid_cap);
+        case 8: return gc_launch<8>(a, garble, stream, grid_cap);
         default: return hipErrorInvalidValue;
     }
 }
 
-hipError_t launch_gc_garble(const GcArgs& a, hipStream_t stream) { return gc_dispatch(a, true, stream); }
+hipError_t launch_gc_garble(const GcArgs& a, hipStream_t stream, int grid_cap) {
+    return gc_dispatch(a, true, stream, grid_cap);
+}
 
-hipError_t launch_gc_eval(const GcArgs& a, hipStream_t stream) { return gc_dispatch(a, false, stream); }
+hipError_t launch_gc_eval(const GcArgs& a, hipStream_t stream, int grid_cap) {
+    return gc_dispatch(a, false, stream, grid_cap);
+}
 
 }  // namespace fhh

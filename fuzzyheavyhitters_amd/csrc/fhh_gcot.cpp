@@ -191,16 +191,16 @@ int ot_run(fhh_ctx* ctx, OtArgs a, uint64_t m, OtOut* tr) {
         a.ss_corr = ctx->ot_buf[4].as<uint4>();
         HIP_TRY(ctx, launch_ss_ggm(a, ctx->stream));
     }
-    HIP_TRY(ctx, launch_ot_recv_expand(a, ctx->stream));     // receiver -> sender: U
-    HIP_TRY(ctx, launch_ot_send_expand(a, ctx->stream));     // sender: Q
+    HIP_TRY(ctx, launch_ot_recv_expand(a, ctx->stream, ctx->protocol_grid));     // receiver -> sender: U
+    HIP_TRY(ctx, launch_ot_send_expand(a, ctx->stream, ctx->protocol_grid));     // sender: Q
     if (a.mode == 5) {   // the correlation, left tile-major in Q / T for the r06 garbled table
     } else if (a.mode == 4) {   // the correlation itself: q_j, t_j (no hash, no y)
-        HIP_TRY(ctx, launch_ot_rows_out(a, true, ctx->stream));
-        HIP_TRY(ctx, launch_ot_rows_out(a, false, ctx->stream));
+        HIP_TRY(ctx, launch_ot_rows_out(a, true, ctx->stream, ctx->protocol_grid));
+        HIP_TRY(ctx, launch_ot_rows_out(a, false, ctx->stream, ctx->protocol_grid));
     } else {
-        HIP_TRY(ctx, launch_ot_send_hash_rows(a, ctx->stream));  // sender -> receiver: y (Y0 | Y1)
-        if (a.mode == 3) HIP_TRY(ctx, launch_cot_fe255_finish(a, ctx->stream));
-        HIP_TRY(ctx, launch_ot_recv_hash_rows(a, ctx->stream));
+        HIP_TRY(ctx, launch_ot_send_hash_rows(a, ctx->stream, ctx->protocol_grid));  // sender -> receiver: y (Y0 | Y1)
+        if (a.mode == 3) HIP_TRY(ctx, launch_cot_fe255_finish(a, ctx->stream, ctx->protocol_grid));
+        HIP_TRY(ctx, launch_ot_recv_hash_rows(a, ctx->stream, ctx->protocol_grid));
     }
     if (tr) {
         tr->U = a.U;
@@ -242,8 +242,8 @@ int fhh_gc_equality_device(fhh_ctx* ctx, const fhh_gc_batch* b) {
     GcArgs a;
     rc = gc_args(ctx, b, a);
     if (rc) return rc;
-    HIP_TRY(ctx, launch_gc_garble(a, ctx->stream));
-    HIP_TRY(ctx, launch_gc_eval(a, ctx->stream));
+    HIP_TRY(ctx, launch_gc_garble(a, ctx->stream, ctx->protocol_grid));
+    HIP_TRY(ctx, launch_gc_eval(a, ctx->stream, ctx->protocol_grid));
     return ctx_sync(ctx);
 }
 
@@ -593,9 +593,9 @@ int fhh_ev_ot_labels(fhh_ctx* ctx, const fhh_ev_cfg* cfg, const uint8_t** u_dev,
         a.choices = P.planes.as<uint32_t>();
         a.out = P.plan.tile_major ? nullptr : P.labels.as<uint4>();
         HIP_TRY(ctx, party_ggm(P, a, true, ctx->stream));
-        HIP_TRY(ctx, launch_ot_recv_expand(a, ctx->stream));        // T, U
+        HIP_TRY(ctx, launch_ot_recv_expand(a, ctx->stream, ctx->protocol_grid));        // T, U
         // its active labels t_j: row-major for the circuit; the r06 table reads T tile-major
-        if (!P.plan.tile_major) HIP_TRY(ctx, launch_ot_rows_out(a, false, ctx->stream));
+        if (!P.plan.tile_major) HIP_TRY(ctx, launch_ot_rows_out(a, false, ctx->stream, ctx->protocol_grid));
     }
     rc = ctx_sync(ctx);
     if (rc) return rc;
@@ -676,8 +676,9 @@ int fhh_gb_ot_labels(fhh_ctx* ctx, const fhh_gb_cfg* cfg, const uint8_t* u_dev, 
         for (int c = 0; c < 4; c++) a.s[c] = P.s[0][c];
         a.sx = P.plan.tile_major ? nullptr : P.labels.p;
         HIP_TRY(ctx, party_ggm(P, a, false, ctx->stream));
-        HIP_TRY(ctx, launch_ot_send_expand(a, ctx->stream));      // Q from U
-        if (!P.plan.tile_major) HIP_TRY(ctx, launch_ot_rows_out(a, true, ctx->stream));   // the zero labels q_j (the circuit)
+        HIP_TRY(ctx, launch_ot_send_expand(a, ctx->stream, ctx->protocol_grid));      // Q from U
+        // the zero labels q_j (the circuit)
+        if (!P.plan.tile_major) HIP_TRY(ctx, launch_ot_rows_out(a, true, ctx->stream, ctx->protocol_grid));
     }
     rc = ctx_sync(ctx);
     if (rc) return rc;
@@ -695,7 +696,9 @@ int fhh_gb_garble(fhh_ctx* ctx, const uint8_t** gc_msg_dev, uint64_t* gc_msg_byt
     PartyState* Pp = ctx->party;
     if (!Pp || Pp->role != 0 || Pp->step != 1) return ctx->fail(FHH_E_STATE, "gb_garble: call after fhh_gb_ot_labels");
     PartyState& P = *Pp;
-    if (P.tests) HIP_TRY(ctx, P.plan.table ? launch_gt_garble(P.g, ctx->stream) : launch_gc_garble(P.g, ctx->stream));
+    if (P.tests)
+        HIP_TRY(ctx, P.plan.table ? launch_gt_garble(P.g, ctx->stream, ctx->protocol_grid)
+                                  : launch_gc_garble(P.g, ctx->stream, ctx->protocol_grid));
     rc = party_partials_to_host(ctx, P);
     if (rc) return rc;
     rc = ctx_sync(ctx);
@@ -749,7 +752,9 @@ int fhh_ev_evaluate(fhh_ctx* ctx, const uint8_t* gc_msg_dev, uint64_t gc_len, co
         g.out_packed = P.choices2.as<uint32_t>();
         g.out_dup = P.plan.per2;
     }
-    if (P.tests) HIP_TRY(ctx, P.plan.table ? launch_gt_eval(g, ctx->stream) : launch_gc_eval(g, ctx->stream));
+    if (P.tests)
+        HIP_TRY(ctx, P.plan.table ? launch_gt_eval(g, ctx->stream, ctx->protocol_grid)
+                                  : launch_gc_eval(g, ctx->stream, ctx->protocol_grid));
     rc = party_partials_to_host(ctx, P);
     if (rc) return rc;
     // 3. OT 2's receiver: choice = the GC output (collect.rs:461-471); T and U reused
@@ -759,7 +764,7 @@ int fhh_ev_evaluate(fhh_ctx* ctx, const uint8_t* gc_msg_dev, uint64_t gc_len, co
         OtArgs a = party_ot(P, 1, P.m2);
         a.choices = P.choices2.as<uint32_t>();
         HIP_TRY(ctx, party_ggm(P, a, true, ctx->stream));
-        HIP_TRY(ctx, launch_ot_recv_expand(a, ctx->stream));
+        HIP_TRY(ctx, launch_ot_recv_expand(a, ctx->stream, ctx->protocol_grid));
     }
     rc = ctx_sync(ctx);
     if (rc) return rc;
@@ -794,9 +799,9 @@ int fhh_gb_ot_shares(fhh_ctx* ctx, const uint8_t* u_dev, uint64_t u_len, const u
         a.sx = party_vals(P);
         a.Y0 = P.Y.as<uint4>();
         HIP_TRY(ctx, party_ggm(P, a, false, ctx->stream));
-        HIP_TRY(ctx, launch_ot_send_expand(a, ctx->stream));
-        HIP_TRY(ctx, launch_ot_send_hash_rows(a, ctx->stream));
-        if (P.last) HIP_TRY(ctx, launch_cot_fe255_finish(a, ctx->stream));
+        HIP_TRY(ctx, launch_ot_send_expand(a, ctx->stream, ctx->protocol_grid));
+        HIP_TRY(ctx, launch_ot_send_hash_rows(a, ctx->stream, ctx->protocol_grid));
+        if (P.last) HIP_TRY(ctx, launch_cot_fe255_finish(a, ctx->stream, ctx->protocol_grid));
     }
     P.covered = P.c_off + P.C;
     rc = ctx_sync(ctx);
@@ -823,7 +828,7 @@ int fhh_ev_ot_shares(fhh_ctx* ctx, const uint8_t* y_dev, uint64_t y_len) {
         a.choices = P.choices2.as<uint32_t>();
         a.Y0 = const_cast<uint4*>(reinterpret_cast<const uint4*>(y_dev));
         a.out = reinterpret_cast<uint4*>(party_vals(P));
-        HIP_TRY(ctx, launch_ot_recv_hash_rows(a, ctx->stream));
+        HIP_TRY(ctx, launch_ot_recv_hash_rows(a, ctx->stream, ctx->protocol_grid));
     }
     P.covered = P.c_off + P.C;
     rc = ctx_sync(ctx);

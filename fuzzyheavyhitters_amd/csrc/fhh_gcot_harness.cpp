@@ -277,11 +277,11 @@ int fhh_gc_cot_host(fhh_ctx* ctx, uint64_t n, uint32_t bits, const uint8_t* gb_b
         g.sh_gb = dsh.as<uint64_t>();
         g.sh_y = g.sh_gb + n;
     }
-    HIP_TRY(ctx, launch_gc_garble(g, ctx->stream));
+    HIP_TRY(ctx, launch_gc_garble(g, ctx->stream, ctx->protocol_grid));
     g.ev_labels = da.as<uint4>();
     g.sh_gb = nullptr;
     if (share) g.sh_ev = dsh.as<uint64_t>() + 2 * n;
-    HIP_TRY(ctx, launch_gc_eval(g, ctx->stream));
+    HIP_TRY(ctx, launch_gc_eval(g, ctx->stream, ctx->protocol_grid));
     rc = ctx_sync(ctx);
     if (rc) return rc;
     HIP_TRY(ctx, hipMemcpy(out, dout.p, n, hipMemcpyDeviceToHost));
@@ -359,18 +359,18 @@ static int gt_cot_host(fhh_ctx* ctx, uint64_t n, uint32_t bits, const uint8_t* g
     g.gt_msgs = dm.as<uint64_t>();
     g.ring32 = plan.ring32 ? 1u : 0u;
     g.sh_gb = dsh.as<uint64_t>();
-    HIP_TRY(ctx, launch_gt_garble(g, ctx->stream));
+    HIP_TRY(ctx, launch_gt_garble(g, ctx->stream, ctx->protocol_grid));
     g.ev_labels = tm ? ctx->ot_buf[0].as<uint4>() : da.as<uint4>();
     g.sh_gb = nullptr;
     g.sh_ev = dsh.as<uint64_t>() + n;
-    HIP_TRY(ctx, launch_gt_eval(g, ctx->stream));
+    HIP_TRY(ctx, launch_gt_eval(g, ctx->stream, ctx->protocol_grid));
     if (tm && (ev_zero || ev_active)) {   // the transcript's row-major labels, after the fact (tests only)
         a.m = m;
         a.mp = ot_padded(m);
         a.T = ctx->ot_buf[0].as<uint4>();
         a.Q = ctx->ot_buf[2].as<uint4>();
-        HIP_TRY(ctx, launch_ot_rows_out(a, true, ctx->stream));
-        HIP_TRY(ctx, launch_ot_rows_out(a, false, ctx->stream));
+        HIP_TRY(ctx, launch_ot_rows_out(a, true, ctx->stream, ctx->protocol_grid));
+        HIP_TRY(ctx, launch_ot_rows_out(a, false, ctx->stream, ctx->protocol_grid));
     }
     rc = ctx_sync(ctx);
     if (rc) return rc;

@@ -1227,6 +1227,30 @@ int fhh_set_table_row_major(fhh_ctx* ctx, int on) {
     return FHH_OK;
 }
 
+int fhh_set_protocol_grid(fhh_ctx* ctx, int blocks) {
+    CTX_CHECK(ctx);
+    if (blocks < 0) return ctx->fail(FHH_E_ARG, "set_protocol_grid: blocks must be >= 0 (0: the device rule)");
+    if (ctx->group) {   // the shards launch; the group ctx keeps the value for fhh_protocol_grid
+        const int rc = group_each(ctx, fhh_set_protocol_grid, blocks);
+        if (rc) return rc;
+    }
+    ctx->protocol_grid = blocks;
+    return FHH_OK;
+}
+
+int fhh_protocol_grid(fhh_ctx* ctx, int family, uint64_t need, int* grid) {
+    CTX_CHECK(ctx);
+    if (family < 0 || family >= (int)kGridFamilies || !grid)
+        return ctx->fail(FHH_E_ARG, "protocol_grid: family must be in [0, " + std::to_string((int)kGridFamilies) +
+                                        ") and grid non-null");
+    if (!ctx->group) {   // the CU count is the ctx's device's (a multi-device ctx: the current device's)
+        const int rc = ctx_set_device(ctx);
+        if (rc) return rc;
+    }
+    *grid = protocol_grid(need, (ProtocolGridFamily)family, ctx->protocol_grid);
+    return FHH_OK;
+}
+
 int fhh_expand_layout(int variant, int grid_blocks, uint32_t njobs, const uint32_t* n_live, uint32_t nw, uint32_t* g,
                       uint32_t* wpi, uint64_t* total) {
     if (variant < 0 || variant >= expand_variant_count() || !expand_threads(variant)) {

@@ -455,13 +455,36 @@ struct OtArgs {
     uint4* ss_leaf;
     uint4* ss_corr;
 };
+// ---- the launch grid of the GC / OT kernels whose workgroups stride over their work -------------------------
+// CU count of the current device, queried once per device (fhh_ot.hip; 256 where the query fails)
+int device_cus();
+// the launcher families (fhh_protocol_grid's `family`) and the workgroups each may keep per CU
+enum ProtocolGridFamily {
+    kGridOtExpand = 0,    // k_ot_*_expand_cc, k_ss_*_expand: 256 threads, 20 KiB of LDS
+    kGridOtHash = 1,      // k_ot_send_hash_rows, k_ot_recv_hash_rows: one 160-KiB workgroup per CU
+    kGridOtRowsOut = 2,   // k_ot_rows_out
+    kGridCotFinish = 3,   // k_cot_fe255_finish
+    kGridGc = 4,          // k_gc_garble, k_gc_garble_cot, k_gc_eval
+    kGridGtTm = 5,        // k_gt_garble_tm, k_gt_eval_tm: one 160-KiB workgroup per CU
+    kGridGtRows = 6,      // k_gt_garble, k_gt_eval (row-major labels)
+    kGridFamilies = 7
+};
+constexpr uint32_t kGridPerCu[kGridFamilies] = {8, 1, 8, 8, 8, 1, 8};
+// The one grid rule: `need` workgroups, at most per_cu for each CU of the current device, at least one; a test
+// override `cap_blocks` >= 1 (fhh_set_protocol_grid) lowers the device's limit to that many workgroups, 0 leaves it
+inline int protocol_grid(uint64_t need, ProtocolGridFamily family, int cap_blocks) {
+    uint64_t cap = (uint64_t)device_cus() * kGridPerCu[family];
+    if (cap_blocks > 0 && (uint64_t)cap_blocks < cap) cap = (uint64_t)cap_blocks;
+    return (int)(need < cap ? (need ? need : 1) : cap);
+}
+// The launchers below that size their grid by this rule take the ctx's override as `grid_cap` (0: none)
 // SoftSpoken GGM trees of both parties from rk / s (one workgroup; before the expands)
 hipError_t launch_ss_ggm(const OtArgs& a, hipStream_t stream);
-hipError_t launch_ot_recv_expand(const OtArgs& a, hipStream_t stream);
-hipError_t launch_ot_send_expand(const OtArgs& a, hipStream_t stream);
+hipError_t launch_ot_recv_expand(const OtArgs& a, hipStream_t stream, int grid_cap);
+hipError_t launch_ot_send_expand(const OtArgs& a, hipStream_t stream, int grid_cap);
 // the hashes reading T / Q in row form with the transpose fused in (no Tt / Qt pass)
-hipError_t launch_ot_send_hash_rows(const OtArgs& a, hipStream_t stream);
-hipError_t launch_ot_recv_hash_rows(const OtArgs& a, hipStream_t stream);
+hipError_t launch_ot_send_hash_rows(const OtArgs& a, hipStream_t stream, int grid_cap);
+hipError_t launch_ot_recv_hash_rows(const OtArgs& a, hipStream_t stream, int grid_cap);
 // *word &= mask (one lane; the tail of a choice-bit buffer)
 hipError_t launch_mask_word(uint32_t* word, uint32_t mask, hipStream_t stream);
 // the 128 Chou–Orlandi base OTs of OT extension k (fhh_base_ot.cpp)
@@ -472,13 +495,13 @@ hipError_t launch_ot_level_keys(uint64_t prf, uint32_t level, uint32_t salt, con
 // mode 3's second pass (the garbler, FieldElm share): per test t, V = H(q_2t) || H(q_2t+1) (32
 // big-endian bytes, sx) mod p255 -> sx pair = V + mask (its node value, a canonical BlockPair), Y0 pair
 // ^= (mask ? V + 1 : V - 1); tests = the active OT pairs (ctl-aware as the hashes)
-hipError_t launch_cot_fe255_finish(const OtArgs& a, hipStream_t stream);
+hipError_t launch_cot_fe255_finish(const OtArgs& a, hipStream_t stream, int grid_cap);
 // mode 4: the tile-major Q (sender: -> sx) or T (receiver: -> out) as one 16-B row per OT
-hipError_t launch_ot_rows_out(const OtArgs& a, bool sender, hipStream_t stream);
-hipError_t launch_gc_garble(const GcArgs& a, hipStream_t stream);
-hipError_t launch_gc_eval(const GcArgs& a, hipStream_t stream);
-hipError_t launch_gt_garble(const GcArgs& a, hipStream_t stream);   // r05d garbled table
-hipError_t launch_gt_eval(const GcArgs& a, hipStream_t stream);
+hipError_t launch_ot_rows_out(const OtArgs& a, bool sender, hipStream_t stream, int grid_cap);
+hipError_t launch_gc_garble(const GcArgs& a, hipStream_t stream, int grid_cap);
+hipError_t launch_gc_eval(const GcArgs& a, hipStream_t stream, int grid_cap);
+hipError_t launch_gt_garble(const GcArgs& a, hipStream_t stream, int grid_cap);   // r05d garbled table
+hipError_t launch_gt_eval(const GcArgs& a, hipStream_t stream, int grid_cap);
 // sums[c] += the u32 node values vals [C][n] of child c, as u64 (sums zeroed by the caller; Z_2^32 table, b = 3, 4)
 hipError_t launch_ring32_child_sums(const uint32_t* vals, uint64_t n, uint64_t C, uint64_t* sums, hipStream_t stream);
 hipError_t launch_ring32_child_partials(const uint32_t* vals, uint64_t n, uint64_t G, const LoopCtl* ctl, uint64_t g_off,

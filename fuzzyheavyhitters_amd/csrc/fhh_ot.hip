@@ -959,8 +959,9 @@ hipError_t launch_ot_level_keys(uint64_t prf, uint32_t level, uint32_t salt, con
 }
 
 // CU count of the current device, queried once per device (the level loop launches these
-// kernels thousands of times per crawl)
-static int device_cus() {
+// kernels thousands of times per crawl). Where hipGetDevice or the attribute query fails it answers 256 instead of
+// the error (the GC launchers' own query used to return it): the launch that follows reports the device's state
+int device_cus() {
     static std::atomic<int> cache[64] = {};   // shard threads of a multi-device ctx share it
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
@@ -974,34 +975,34 @@ static int device_cus() {
 
 
 // the ChaCha expands: 256-thread workgroups (20 KiB of LDS staging, ~70 VGPRs), 8 per CU, waves stride over the items
-static int ot_cc_grid(uint64_t items) {
-    const uint64_t wpb = kOtCcThreads / 64, need = (items + wpb - 1) / wpb, cap = (uint64_t)device_cus() * 8;
-    return (int)(need < cap ? (need ? need : 1) : cap);
+static int ot_cc_grid(uint64_t items, int grid_cap) {
+    const uint64_t wpb = kOtCcThreads / 64;
+    return protocol_grid((items + wpb - 1) / wpb, kGridOtExpand, grid_cap);
 }
 
-hipError_t launch_ot_recv_expand(const OtArgs& a, hipStream_t stream) {
+hipError_t launch_ot_recv_expand(const OtArgs& a, hipStream_t stream, int grid_cap) {
     if (a.ctr_off % 4) return hipErrorInvalidValue;   // ChaCha counters per 512-OT tile
     if (a.ss_k == 2 || a.ss_k == 4) {   // SoftSpoken: one wave per tile (k = 2) or tile pair (k = 4)
         const uint64_t tiles = a.mp / 512;
-        if (a.ss_k == 2) hipLaunchKernelGGL(k_ss_recv_expand<2>, dim3(ot_cc_grid(tiles)), dim3(kOtCcThreads), 0, stream, a);
-        else hipLaunchKernelGGL(k_ss_recv_expand<4>, dim3(ot_cc_grid((tiles + 1) / 2)), dim3(kOtCcThreads), 0, stream, a);
+        if (a.ss_k == 2) hipLaunchKernelGGL(k_ss_recv_expand<2>, dim3(ot_cc_grid(tiles, grid_cap)), dim3(kOtCcThreads), 0, stream, a);
+        else hipLaunchKernelGGL(k_ss_recv_expand<4>, dim3(ot_cc_grid((tiles + 1) / 2, grid_cap)), dim3(kOtCcThreads), 0, stream, a);
         return hipGetLastError();
     }
     if (a.ss_k > 1) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_ot_recv_expand_cc, dim3(ot_cc_grid(2 * (a.mp / 512))), dim3(kOtCcThreads), 0, stream, a);
+    hipLaunchKernelGGL(k_ot_recv_expand_cc, dim3(ot_cc_grid(2 * (a.mp / 512), grid_cap)), dim3(kOtCcThreads), 0, stream, a);
     return hipGetLastError();
 }
 
-hipError_t launch_ot_send_expand(const OtArgs& a, hipStream_t stream) {
+hipError_t launch_ot_send_expand(const OtArgs& a, hipStream_t stream, int grid_cap) {
     if (a.ctr_off % 4) return hipErrorInvalidValue;
     if (a.ss_k == 2 || a.ss_k == 4) {
         const uint64_t tiles = a.mp / 512;
-        if (a.ss_k == 2) hipLaunchKernelGGL(k_ss_send_expand<2>, dim3(ot_cc_grid(tiles)), dim3(kOtCcThreads), 0, stream, a);
-        else hipLaunchKernelGGL(k_ss_send_expand<4>, dim3(ot_cc_grid((tiles + 1) / 2)), dim3(kOtCcThreads), 0, stream, a);
+        if (a.ss_k == 2) hipLaunchKernelGGL(k_ss_send_expand<2>, dim3(ot_cc_grid(tiles, grid_cap)), dim3(kOtCcThreads), 0, stream, a);
+        else hipLaunchKernelGGL(k_ss_send_expand<4>, dim3(ot_cc_grid((tiles + 1) / 2, grid_cap)), dim3(kOtCcThreads), 0, stream, a);
         return hipGetLastError();
     }
     if (a.ss_k > 1) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_ot_send_expand_cc, dim3(ot_cc_grid(a.mp / 512)), dim3(kOtCcThreads), 0, stream, a);
+    hipLaunchKernelGGL(k_ot_send_expand_cc, dim3(ot_cc_grid(a.mp / 512, grid_cap)), dim3(kOtCcThreads), 0, stream, a);
     return hipGetLastError();
 }
 
@@ -1024,15 +1025,14 @@ hipError_t launch_mask_word(uint32_t* word, uint32_t mask, hipStream_t stream) {
 }
 
 // the hashes: one 1024-thread workgroup per CU (160 KiB of LDS), waves stride over the tiles
-static int ot_rows_grid(const OtArgs& a) {
+static int ot_rows_grid(const OtArgs& a, int grid_cap) {
     const uint64_t tiles = (a.m + 32 * kOtTileWords - 1) / (32 * kOtTileWords);
-    const uint64_t need = (tiles + kOtWaves - 1) / kOtWaves, cap = (uint64_t)device_cus();
-    return (int)(need < cap ? (need ? need : 1) : cap);
+    return protocol_grid((tiles + kOtWaves - 1) / kOtWaves, kGridOtHash, grid_cap);
 }
 
-hipError_t launch_ot_send_hash_rows(const OtArgs& a, hipStream_t stream) {
+hipError_t launch_ot_send_hash_rows(const OtArgs& a, hipStream_t stream, int grid_cap) {
     if (a.mp % 8192 != 0) return hipErrorInvalidValue;   // tiles of 16 words stay inside a row
-    const dim3 g(ot_rows_grid(a)), b(kOtRowsThreads);
+    const dim3 g(ot_rows_grid(a, grid_cap)), b(kOtRowsThreads);
     switch (a.mode) {
         case 0: hipLaunchKernelGGL(k_ot_send_hash_rows<0>, g, b, 0, stream, a); break;
         case 1: hipLaunchKernelGGL(k_ot_send_hash_rows<1>, g, b, 0, stream, a); break;
@@ -1043,9 +1043,9 @@ hipError_t launch_ot_send_hash_rows(const OtArgs& a, hipStream_t stream) {
     return hipGetLastError();
 }
 
-hipError_t launch_ot_recv_hash_rows(const OtArgs& a, hipStream_t stream) {
+hipError_t launch_ot_recv_hash_rows(const OtArgs& a, hipStream_t stream, int grid_cap) {
     if (a.mp % 8192 != 0) return hipErrorInvalidValue;
-    const dim3 g(ot_rows_grid(a)), b(kOtRowsThreads);
+    const dim3 g(ot_rows_grid(a, grid_cap)), b(kOtRowsThreads);
     switch (a.mode) {
         case 0: hipLaunchKernelGGL(k_ot_recv_hash_rows<0>, g, b, 0, stream, a); break;
         case 1: hipLaunchKernelGGL(k_ot_recv_hash_rows<1>, g, b, 0, stream, a); break;
@@ -1056,20 +1056,20 @@ hipError_t launch_ot_recv_hash_rows(const OtArgs& a, hipStream_t stream) {
     return hipGetLastError();
 }
 
-hipError_t launch_ot_rows_out(const OtArgs& a, bool sender, hipStream_t stream) {
+hipError_t launch_ot_rows_out(const OtArgs& a, bool sender, hipStream_t stream, int grid_cap) {
     if (a.mp % 8192 != 0) return hipErrorInvalidValue;   // tiles of 16 words stay inside a row
     const uint64_t tiles = (a.m + 32 * kOtTileWords - 1) / (32 * kOtTileWords);
-    const uint64_t wpb = kOtOutThreads / 64, need = (tiles + wpb - 1) / wpb, cap = (uint64_t)device_cus() * 8;
-    hipLaunchKernelGGL(k_ot_rows_out, dim3((int)(need < cap ? (need ? need : 1) : cap)), dim3(kOtOutThreads), 0, stream,
-                       a, sender ? 1 : 0);
+    const uint64_t wpb = kOtOutThreads / 64;
+    hipLaunchKernelGGL(k_ot_rows_out, dim3(protocol_grid((tiles + wpb - 1) / wpb, kGridOtRowsOut, grid_cap)),
+                       dim3(kOtOutThreads), 0, stream, a, sender ? 1 : 0);
     return hipGetLastError();
 }
 
-hipError_t launch_cot_fe255_finish(const OtArgs& a, hipStream_t stream) {
+hipError_t launch_cot_fe255_finish(const OtArgs& a, hipStream_t stream, int grid_cap) {
     if (a.mode != 3 || a.m % 2) return hipErrorInvalidValue;
     const uint64_t tests = a.m / 2;
-    const uint64_t need = (tests + 255) / 256, cap = (uint64_t)device_cus() * 8;
-    hipLaunchKernelGGL(k_cot_fe255_finish, dim3((int)(need < cap ? (need ? need : 1) : cap)), dim3(256), 0, stream, a);
+    hipLaunchKernelGGL(k_cot_fe255_finish, dim3(protocol_grid((tests + 255) / 256, kGridCotFinish, grid_cap)), dim3(256), 0,
+                       stream, a);
     return hipGetLastError();
 }
 

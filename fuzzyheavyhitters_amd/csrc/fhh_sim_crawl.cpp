@@ -743,11 +743,11 @@ int gc_chunk(Loop& S, const Level& L, const GcLevel& G, uint64_t k) {
         g.node_off = 0;
         g.ring32 = p.ring32 ? 1u : 0u;   // (row-major: u32 values [tests] in gc_val, u32 messages)
         g.sh_gb = fused ? nullptr : S.gc_val[0].as<uint64_t>();
-        HIP_TRY(c0, launch_gt_garble(g, c0->stream));
+        HIP_TRY(c0, launch_gt_garble(g, c0->stream, c0->protocol_grid));
         g.ev_labels = p.tile_major ? c0->ot_buf[0].as<uint4>() : S.gc_evact.as<uint4>();
         g.sh_gb = nullptr;
         g.sh_ev = fused ? nullptr : S.gc_val[1].as<uint64_t>();
-        HIP_TRY(c0, launch_gt_eval(g, c0->stream));
+        HIP_TRY(c0, launch_gt_eval(g, c0->stream, c0->protocol_grid));
         if (p.ring32 && !fused)   // the row-major Z_2^32 values into the partials' low sums
             for (uint32_t sv = 0; sv < 2; sv++)
                 HIP_TRY(c0, launch_ring32_child_partials(S.gc_val[sv].as<uint32_t>(), c0->n, Gc,
@@ -760,7 +760,7 @@ int gc_chunk(Loop& S, const Level& L, const GcLevel& G, uint64_t k) {
         g.sh_y = S.gc_y.as<uint64_t>();
     }
     if (!p.table) {
-        HIP_TRY(c0, launch_gc_garble(g, c0->stream));
+        HIP_TRY(c0, launch_gc_garble(g, c0->stream, c0->protocol_grid));
         if (p.real_ot) {
             g.ev_labels = S.gc_evact.as<uint4>();
             g.sh_gb = nullptr;
@@ -774,7 +774,7 @@ int gc_chunk(Loop& S, const Level& L, const GcLevel& G, uint64_t k) {
                 g.out_dup = p.per2;
             }
         }
-        HIP_TRY(c0, launch_gc_eval(g, c0->stream));
+        HIP_TRY(c0, launch_gc_eval(g, c0->stream, c0->protocol_grid));
     }
     ChildArgs ca = G.a;   // this chunk's children
     ca.c_off = g_off;

@@ -944,6 +944,29 @@ int fhh_set_expand_grid(fhh_ctx* ctx, int blocks);
  * (tools/gt_tm_ab.py). No effect at b <= 2. The party ABI (fhh_gb_* / fhh_ev_*) keeps the row-major labels at
  * b = 3, 4 whatever the flag says. The device loop follows the first ctx. FHH_E_ARG unless on is 0 or 1. */
 int fhh_set_table_row_major(fhh_ctx* ctx, int on);
+/* Test / diagnostic ABI, not a product knob and not for production use: blocks >= 1 caps the launch grid of
+ * every GC / OT kernel whose workgroups stride over their work (the OT expands, hashes, k_ot_rows_out,
+ * k_cot_fe255_finish, the circuit and the table kernels: the FHH_GRID_* families below) at `blocks` workgroups
+ * instead of a multiple of the device's CU count, so that a few thousand OTs or tests send those loops through
+ * the second and later trips they take at 100k-1M clients (tests/test_protocol_grid.py). Every output is the
+ * same under any cap; a small cap only makes the launches slow, and one above the device rule changes nothing.
+ * blocks = 0 restores the device rule. The
+ * fixed-size launches (the GGM trees, the level keys) are not affected. Applies to every later launch of the
+ * ctx, on each shard of a multi-device ctx; the device loop follows the first ctx. fhh_set_variant keeps it.
+ * FHH_E_ARG, with the ctx unchanged, for a NULL ctx or blocks < 0. */
+int fhh_set_protocol_grid(fhh_ctx* ctx, int blocks);
+/* Test / diagnostic ABI, host arithmetic on the ctx's device properties: the grid the launchers of `family`
+ * use for a launch that needs `need` workgroups: min(need, CUs x the family's workgroups per CU, and blocks
+ * under fhh_set_protocol_grid), and at least 1. FHH_E_ARG for a NULL ctx, an unknown family
+ * or a NULL grid. */
+#define FHH_GRID_OT_EXPAND 0   /* k_ot_recv/send_expand_cc, k_ss_recv/send_expand: 4 waves, 8 workgroups per CU */
+#define FHH_GRID_OT_HASH 1     /* k_ot_send/recv_hash_rows: 16 waves, 1 per CU                                  */
+#define FHH_GRID_OT_ROWS_OUT 2 /* k_ot_rows_out: 8 per CU                                                       */
+#define FHH_GRID_COT_FINISH 3  /* k_cot_fe255_finish: 256 tests per workgroup, 8 per CU                         */
+#define FHH_GRID_GC 4          /* k_gc_garble, k_gc_garble_cot, k_gc_eval: 1024 tests per workgroup, 8 per CU   */
+#define FHH_GRID_GT_TM 5       /* k_gt_garble_tm, k_gt_eval_tm: 16 tile waves, 1 per CU                         */
+#define FHH_GRID_GT_ROWS 6     /* k_gt_garble, k_gt_eval (row-major labels): 1024 tests per workgroup, 8 per CU */
+int fhh_protocol_grid(fhh_ctx* ctx, int family, uint64_t need, int* grid);
 /* Test / diagnostic ABI, pure host arithmetic (no GPU): the work decomposition k_expand variant
  * `variant` gets on a grid of grid_blocks workgroups for a launch of njobs (<= 8) jobs with n_live[k]
  * live entries each over nw 64-client words — the same function the host launches and the device loop's

@@ -150,10 +150,19 @@ int orc_aes_ni_available(void) {
     return (c & bit_AES) ? 1 : 0;
 }
 
+static inline int ni_ready(void) { return __atomic_load_n(&g_ni_ready, __ATOMIC_ACQUIRE); }
+/* One writer, and the flag after the keys (release): the callers reach this from inside parallel loops (the GC / OT
+ * hashes), where a plain flag store let a thread see the flag before the keys, and the first hashes of a process'
+ * first parallel call ran on a half-filled schedule. */
 __attribute__((target("aes,sse4.1"))) static void ni_prepare(void) {
     oracle_init();
-    for (int i = 0; i < 11; i++) g_ni_rk[i] = _mm_loadu_si128((const __m128i*)(g_rk0 + 16 * i));
-    g_ni_ready = 1;
+#pragma omp critical(fhh_oracle_ni)
+    {
+        if (!ni_ready()) {
+            for (int i = 0; i < 11; i++) g_ni_rk[i] = _mm_loadu_si128((const __m128i*)(g_rk0 + 16 * i));
+            __atomic_store_n(&g_ni_ready, 1, __ATOMIC_RELEASE);
+        }
+    }
 }
 
 /* One non-pipelined AES-NI block, like the reference's single-block `encrypt_block`. */
@@ -172,7 +181,7 @@ __attribute__((target("aes,sse4.1"))) static inline __m128i ni_aes0(__m128i x) {
 }
 
 __attribute__((target("aes,sse4.1"))) void orc_aes128_zero_encrypt_ni(const uint8_t in[16], uint8_t out[16]) {
-    if (!g_ni_ready) ni_prepare();
+    if (!ni_ready()) ni_prepare();
     __m128i x = _mm_loadu_si128((const __m128i*)in);
     _mm_storeu_si128((__m128i*)out, ni_aes0(x));
 }
@@ -313,7 +322,7 @@ void orc_gen_keys(uint64_t n, uint32_t d, uint32_t L, const uint8_t* left_bits, 
     oracle_init();
     int ni = orc_aes_ni_available();
 #if defined(__x86_64__)
-    if (ni && !g_ni_ready) ni_prepare();
+    if (ni && !ni_ready()) ni_prepare();
 #endif
     if (nthreads <= 0) nthreads = omp_get_max_threads();
 #pragma omp parallel for schedule(dynamic, 16) num_threads(nthreads)
@@ -384,7 +393,7 @@ uint64_t orc_level_expand(uint64_t n, uint32_t d, uint32_t L, uint32_t level, co
     oracle_init();
 #if defined(__x86_64__)
     if (use_ni && !orc_aes_ni_available()) use_ni = 0;
-    if (use_ni && !g_ni_ready) ni_prepare();
+    if (use_ni && !ni_ready()) ni_prepare();
 #else
     use_ni = 0;
 #endif

@@ -81,21 +81,8 @@ def test_oracle_garbling_is_input_independent(oracle):
                                     (500, 5), (300, 6), (130, 7)])
 def test_gpu_gc_bit_exact(oracle, n, bits):
     import fuzzyheavyhitters_amd as fhh
-    from fuzzyheavyhitters_amd import gc
-    rng = np.random.default_rng(n * 10 + bits)
-    g, e = _cases(rng, n, bits)
-    kc = fhh.KeyCollection(8, 1)
-    # label_nonce 0 / 1 << 20 (multiples of the label counter stride: the label passes share AES
-    # rounds 1-2) and 123 (unaligned: some lanes' counters carry out of byte 0, full rounds)
-    for nonce, mask in ((123, 0), (123, 1), (0, 1), (1 << 20, 0)):
-        out, tr = gc.equality_test(kc, g, e, mask, KEY, DELTA, label_nonce=nonce, gate_base=77, transcript=True)
-        t, gl, el, d = oracle.gc_garble_eq(g, e, mask, KEY, DELTA, label_nonce=nonce, gate_base=77)
-        assert np.array_equal(tr.tables, t)
-        assert np.array_equal(tr.gb_labels, gl)
-        assert np.array_equal(tr.ev_labels, el)
-        assert np.array_equal(tr.decode, d)
-        assert np.array_equal(out, oracle.gc_eval_eq(t, gl, el, d, gate_base=77))
-        assert np.array_equal(out ^ mask, (g == e).all(axis=1).astype(np.uint8))
+    from protocol_grid_cases import check_gc_bit_exact
+    check_gc_bit_exact(fhh.KeyCollection(8, 1), oracle, n, bits)
 
 
 @pytest.mark.gpu
@@ -287,21 +274,8 @@ def test_gpu_cot_labels_chain_bit_exact(oracle, n, bits):
     """fhh_gc_cot_host (the labels OT + garble + evaluate of one batch) = the oracle chain: zero labels,
     active labels, tables, decoding bits, outputs; an s without the colour bit is refused."""
     import fuzzyheavyhitters_amd as fhh
-    from fuzzyheavyhitters_amd import gc
-    rng = np.random.default_rng(n * 3 + bits)
-    g, e = _cases(rng, n, bits)
-    seeds = rng.integers(0, 256, (128, 2, 16), dtype=np.uint8)
-    s = _colour_s(rng)
-    kc = fhh.KeyCollection(8, 1)
-    with pytest.raises(fhh.FhhError):   # Delta = s needs the colour bit
-        gc.equality_test_cot(kc, g, e, 0, seeds, bytes([s[0] & 0xFE]) + s[1:])
-    for mask, ctr in ((0, 0), (1, 256), (1, 512)):
-        out, tr = gc.equality_test_cot(kc, g, e, mask, seeds, s, gate_base=7, ctr_off=ctr)
-        exp, etr = _oracle_cot_chain(oracle, g, e, mask, seeds, s, gate_base=7, ctr_off=ctr)
-        for k in ("ev_zero", "ev_active", "tables", "decode"):
-            assert np.array_equal(tr[k], etr[k]), k
-        assert np.array_equal(out, exp)
-        assert np.array_equal(out ^ mask, (g == e).all(axis=1).astype(np.uint8))
+    from protocol_grid_cases import check_cot_labels_chain_bit_exact
+    check_cot_labels_chain_bit_exact(fhh.KeyCollection(8, 1), oracle, n, bits)
 
 
 # ---- r05c: the FE share from the circuit's output labels (no second OT at the FE levels) -----------
@@ -337,21 +311,8 @@ def test_gpu_output_label_share_bit_exact(oracle, n, bits):
     """fhh_gc_cot_host's share outputs (k_gc_garble_cot's node values and y, k_gc_eval's node values)
     = the oracle's, bit for bit, with the rest of the transcript unchanged; gb - ev = eq mod p."""
     import fuzzyheavyhitters_amd as fhh
-    from fuzzyheavyhitters_amd import gc
-    rng = np.random.default_rng(n * 5 + bits)
-    g, e = _cases(rng, n, bits)
-    seeds = rng.integers(0, 256, (128, 2, 16), dtype=np.uint8)
-    s = _colour_s(rng)
-    kc = fhh.KeyCollection(8, 1)
-    for mask, ctr in ((0, 0), (1, 256)):
-        out, tr = gc.equality_test_cot(kc, g, e, mask, seeds, s, gate_base=9, ctr_off=ctr, share=True)
-        exp, etr = _oracle_cot_chain(oracle, g, e, mask, seeds, s, gate_base=9, ctr_off=ctr, share=True)
-        for k in ("ev_zero", "ev_active", "tables", "decode", "gb_share", "share_y", "ev_share"):
-            assert np.array_equal(tr[k], etr[k]), k
-        assert np.array_equal(out, exp)
-        eq = (g == e).all(axis=1).astype(np.uint64)
-        assert np.array_equal(((tr["gb_share"].astype(object) - tr["ev_share"].astype(object)) % FE_P)
-                              .astype(np.uint64), eq)
+    from protocol_grid_cases import check_output_label_share_bit_exact
+    check_output_label_share_bit_exact(fhh.KeyCollection(8, 1), oracle, n, bits)
 
 
 # ---- r05d: the FE levels' garbled table (one b-input garbled gate per test) ------------------------

@@ -46,20 +46,8 @@ def test_oracle_ot_transcript_hides_the_unchosen_message(oracle):
 @pytest.mark.parametrize("m", [1, 127, 128, 129, 1000, 8192, 8193, 100_000])
 def test_gpu_ot_bit_exact(oracle, m):
     import fuzzyheavyhitters_amd as fhh
-    from fuzzyheavyhitters_amd import ot
-    ch, x0, x1, seeds, s, delta = _inputs(m, m + 1)
-    kc = fhh.KeyCollection(8, 1)
-    for corr in (False, True):
-        args = dict(x1=None, delta=delta) if corr else dict(x1=x1, delta=None)
-        got, u, y0, y1 = ot.ot_extend(kc, ch, x0, base_seeds=seeds, base_choice=s, tweak_base=11, transcript=True,
-                                      **args)
-        exp, eu, ey0, ey1 = oracle.ot_extend(ch, x0, args["x1"], args["delta"], seeds, s, tweak_base=11,
-                                             transcript=True)
-        assert np.array_equal(got, exp)
-        assert np.array_equal(u, eu)
-        assert np.array_equal(y0, ey0) and np.array_equal(y1, ey1)
-        want = np.where(ch[:, None] == 1, x0 ^ np.frombuffer(delta, np.uint8) if corr else x1, x0)
-        assert np.array_equal(got, want)
+    from protocol_grid_cases import check_ot_bit_exact
+    check_ot_bit_exact(fhh.KeyCollection(8, 1), oracle, m)
 
 
 @pytest.mark.gpu
@@ -249,27 +237,5 @@ def test_gpu_cot_bit_exact(oracle, m):
     """GPU correlated OT (every mode, at a nonzero session counter) = the oracle: both parties'
     outputs and both protocol messages (U, y; mode 4 has no y)."""
     import fuzzyheavyhitters_amd as fhh
-    from fuzzyheavyhitters_amd import ot
-    ch, _, _, seeds, s, delta = _inputs(m, 5 * m + 1)
-    kc = fhh.KeyCollection(8, 1)
-    for ctr_off in (0, 512):
-        got = ot.cot_extend(kc, 1, ch, seeds, s, delta=delta, ctr_off=ctr_off, transcript=True)
-        exp = oracle.cot_extend(oracle.COT_LABELS, ch, seeds, s, delta=delta, ctr_off=ctr_off)
-        for g, e in zip(got, exp):
-            assert np.array_equal(g, e)
-        got = ot.cot_extend(kc, 4, ch, seeds, s, ctr_off=ctr_off, transcript=True)
-        exp = oracle.cot_extend(oracle.COT_RAW, ch, seeds, s, ctr_off=ctr_off)
-        for g, e in zip(got[:3], exp[:3]):   # q, t, U (no y)
-            assert np.array_equal(g, e)
-        for mask in (0, 1):
-            got = ot.cot_extend(kc, 2, ch, seeds, s, mask=mask, ctr_off=ctr_off, transcript=True)
-            exp = oracle.cot_extend(oracle.COT_FE, ch, seeds, s, mask=mask, ctr_off=ctr_off)
-            for g, e in zip(got, exp):
-                assert np.array_equal(g, e)
-        mm = 2 * ((m + 1) // 2)
-        ch2 = np.repeat(ch[: mm // 2], 2)
-        for mask in (0, 1):
-            got = ot.cot_extend(kc, 3, ch2, seeds, s, mask=mask, ctr_off=ctr_off, transcript=True)
-            exp = oracle.cot_extend(oracle.COT_FE255, ch2, seeds, s, mask=mask, ctr_off=ctr_off)
-            for g, e in zip(got, exp):
-                assert np.array_equal(g, e)
+    from protocol_grid_cases import check_cot_bit_exact
+    check_cot_bit_exact(fhh.KeyCollection(8, 1), oracle, m)

@@ -85,21 +85,5 @@ def test_gpu_softspoken_bit_exact(oracle, k, m):
     """GPU SoftSpoken C-OT (every mode, two session counters) = the oracle: both parties' outputs, U and the
     GGM corrections, and y where the mode has one."""
     import fuzzyheavyhitters_amd as fhh
-    from fuzzyheavyhitters_amd import ot
-    ch, seeds, s, delta = _inputs(m, 7 * m + k)
-    kc = fhh.KeyCollection(8, 1)
-    for ctr_off in (0, 512):
-        got = ot.cot_extend(kc, 4, ch, seeds, s, ctr_off=ctr_off, transcript=True, ss_k=k)
-        exp = oracle.cot_extend_ss(k, oracle.COT_RAW, ch, seeds, s, ctr_off=ctr_off)
-        for name, g, e in zip(("q", "t", "U", "y", "corr"), got, exp):
-            if name != "y":
-                assert np.array_equal(g, e), name
-        got = ot.cot_extend(kc, 1, ch, seeds, s, delta=delta, ctr_off=ctr_off, transcript=True, ss_k=k)
-        exp = oracle.cot_extend_ss(k, oracle.COT_LABELS, ch, seeds, s, delta=delta, ctr_off=ctr_off)
-        for g, e in zip(got, exp):
-            assert np.array_equal(g, e)
-        for mask in (0, 1):
-            got = ot.cot_extend(kc, 2, ch, seeds, s, mask=mask, ctr_off=ctr_off, transcript=True, ss_k=k)
-            exp = oracle.cot_extend_ss(k, oracle.COT_FE, ch, seeds, s, mask=mask, ctr_off=ctr_off)
-            for g, e in zip(got, exp):
-                assert np.array_equal(g, e)
+    from protocol_grid_cases import check_softspoken_bit_exact
+    check_softspoken_bit_exact(fhh.KeyCollection(8, 1), oracle, k, m)

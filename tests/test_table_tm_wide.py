@@ -100,29 +100,13 @@ def test_gpu_wide_table_bit_exact(oracle, n, bits, row_major):
     windows straddle two tiles, the second holds 265 live tests; (2650, 3): m = 8064, the last window runs past
     the padded matrix; (4097, 4): nine windows, the last with one live test."""
     import fuzzyheavyhitters_amd as fhh
-    from fuzzyheavyhitters_amd import gc
+    from protocol_grid_cases import check_table_bit_exact
     big = n == GRID_STRIDE
     if big:
         n = _grid_stride_n()
-    rng = np.random.default_rng(n * 13 + bits)
-    g, e = tg._cases(rng, n, bits)
-    seeds = rng.integers(0, 256, (128, 2, 16), dtype=np.uint8)
-    s = tg._colour_s(rng)
     kc = fhh.KeyCollection(8, 1)
     kc.set_table_row_major(row_major)
-    eq = (g == e).all(axis=1).astype(np.uint64)
-    for mask, ctr in (((1, 256),) if big else ((0, 0), (1, 256))):
-        for ring in ((True,) if big else (False, True)):
-            tr = gc.table_cot(kc, g, e, mask, seeds, s, gate_base=13, ctr_off=ctr, ring32=ring)
-            chain = tg._oracle_table_chain_ring32 if ring else tg._oracle_table_chain
-            etr = chain(oracle, g, e, mask, seeds, s, gate_base=13, ctr_off=ctr)
-            for k in ("ev_zero", "ev_active", "msgs", "gb_share", "ev_share"):
-                assert np.array_equal(tr[k], etr[k].astype(tr[k].dtype)), (k, mask, ctr, ring)
-            if ring:
-                assert np.array_equal((tr["gb_share"] - tr["ev_share"]) & 0xFFFFFFFF, eq)
-            else:
-                diff = (tr["gb_share"].astype(object) - tr["ev_share"].astype(object)) % FE_P
-                assert np.array_equal(diff.astype(np.uint64), eq)
+    check_table_bit_exact(kc, oracle, n, bits, big=big)
 
 
 # ---- GPU: the level loop -----------------------------------------------------------------------------------
