@@ -61,6 +61,7 @@ EXPORTS = [
     "fhh_frontier_plan", "fhh_tree_init_at", "fhh_frontier_paths",
     "fhh_retain_clients", "fhh_retain_plan", "fhh_retain_timing",
     "fhh_retain_clients_device", "fhh_retain_plan_device", "fhh_retain_mask_timing",
+    "fhh_gen_keys_ball", "fhh_ball_bounds",
 ]
 
 
@@ -118,9 +119,25 @@ class FhhSimConfig(ctypes.Structure):
 
 
 SOURCES = ("fhh_kernels.hip", "fhh_bincode_out.hip", "fhh_retain.hip", "fhh_retain_mask.hip", "fhh_sketch.hip", "fhh_gc.hip", "fhh_ot.hip",
-           "fhh_loop.hip", "fhh_microbench.hip", "fhh_host.cpp", "fhh_keys_io.cpp", "fhh_retain.cpp",
+           "fhh_loop.hip", "fhh_microbench.hip", "fhh_host.cpp", "fhh_keys_io.cpp", "fhh_retain.cpp", "fhh_ball.cpp",
            "fhh_sim_crawl.cpp", "fhh_sketch_host.cpp",
            "fhh_gcot.cpp", "fhh_gcot_harness.cpp", "fhh_group.cpp", "fhh_comm.cpp", "fhh_base_ot.cpp")
+
+
+# fhh_ball_src.form (include/fhh.h)
+FHH_BALL_BITS, FHH_BALL_COORDS = 0, 1
+
+
+class FhhBallSrc(ctypes.Structure):
+    """fhh_ball_src: a population's points, the ball size and the source of the root seeds (include/fhh.h)."""
+    _fields_ = [
+        ("form", ctypes.c_uint32),
+        ("ball", ctypes.c_uint32),
+        ("points", ctypes.c_void_p),
+        ("root_seeds", u8p),
+        ("seed", ctypes.c_uint8 * 32),
+        ("seed_first", ctypes.c_uint64),
+    ]
 
 
 class FhhSketchBatch(ctypes.Structure):
@@ -317,6 +334,8 @@ def lib():
         "fhh_set_client_base": (i, [vp, u64]),
         "fhh_add_keys": (i, [vp, u64, u8p, u8p, u8p, u8p]),
         "fhh_gen_keys_pair": (i, [vp, vp, u64, u8p, u8p, u8p]),
+        "fhh_gen_keys_ball": (i, [vp, vp, u64, P(FhhBallSrc)]),
+        "fhh_ball_bounds": (i, [u32, u32, u64, P(FhhBallSrc), u8p, u8p, u8p, u64p]),
         "fhh_add_keys_bincode": (i, [vp, u8p, u64]),
         "fhh_reserve_clients": (i, [vp, u64]),
         "fhh_add_keys_bincode_append": (i, [vp, u8p, u64]),

@@ -9,7 +9,7 @@ from dataclasses import dataclass
 
 import numpy as np
 
-from ._lib import FhhError, FhhStats, check, lib, ptr, u32p, u64p
+from ._lib import FHH_BALL_BITS, FHH_BALL_COORDS, FhhBallSrc, FhhError, FhhStats, check, lib, ptr, u32p, u64p
 from .fields import FE255_P, FE_P, limbs10_to_int, int_to_limbs
 
 
@@ -498,6 +498,66 @@ def gen_keys_pair(c0: KeyCollection, c1: KeyCollection, left_bits: np.ndarray, r
     check(lib().fhh_gen_keys_pair(c0.handle, c1.handle, n, ptr(lb), ptr(rb), ptr(rs)), c0.handle)
 
 
+def _ball_src(points: np.ndarray, ball: int, form: str, n_dims: int, data_len: int, root_seeds, seed, seed_first: int):
+    """(fhh_ball_src, n, the arrays it points into) of points in the form's layout: "bits" uint8
+    [n][d][ceil(L / 8)] (`workload.pack_points`), "coords" int16 [n][2] (lat, long)."""
+    if form not in ("bits", "coords"):
+        raise FhhError(f"ball source: unknown form {form!r} (bits, coords)")
+    if form == "bits":
+        pts = np.ascontiguousarray(points, np.uint8)
+        want = (n_dims, (data_len + 7) // 8)
+    else:
+        pts = np.ascontiguousarray(points, np.int16)
+        want = (2,)
+    if pts.ndim != len(want) + 1 or pts.shape[1:] != want:
+        raise FhhError(f"ball source: points of shape {pts.shape}, expected [n]{list(want)} for form {form!r}")
+    n = pts.shape[0]
+    src = FhhBallSrc()
+    src.form = FHH_BALL_BITS if form == "bits" else FHH_BALL_COORDS
+    src.ball = int(ball)
+    src.points = pts.ctypes.data
+    rs = None
+    if root_seeds is not None:
+        rs = np.ascontiguousarray(root_seeds, np.uint8)
+        if rs.shape != (n, n_dims, 2, 2, 16):
+            raise FhhError("ball source: root_seeds must be [n][d][2][2][16]")
+        src.root_seeds = ptr(rs)
+    else:
+        if seed is None or len(bytes(seed)) != 32:
+            raise FhhError("ball source: a 32-byte seed is needed when no root_seeds are given")
+        src.seed[:] = bytes(seed)
+    src.seed_first = int(seed_first)
+    return src, n, (pts, rs)
+
+
+def ball_bounds(points: np.ndarray, ball: int, *, n_dims: int, data_len: int, form: str = "bits", root_seeds=None,
+                seed=None, seed_first: int = 0):
+    """fhh_ball_bounds (host arithmetic, no GPU): (left_bits, right_bits [n][d][L], root_seeds [n][d][2][2][16]) —
+    what `gen_keys_pair` needs to make the keys `gen_keys_ball` makes from the same arguments. Raises on a carry
+    out (the reference panics, ibDCF.rs:182), naming the lowest (client, dim)."""
+    src, n, keep = _ball_src(points, ball, form, n_dims, data_len, root_seeds, seed, seed_first)
+    left = np.zeros((n, n_dims, data_len), np.uint8)
+    right = np.zeros((n, n_dims, data_len), np.uint8)
+    roots = np.zeros((n, n_dims, 2, 2, 16), np.uint8)
+    bad = ctypes.c_uint64()
+    check(lib().fhh_ball_bounds(n_dims, data_len, n, ctypes.byref(src), ptr(left), ptr(right), ptr(roots),
+                                ctypes.byref(bad)))
+    del keep
+    return left, right, roots
+
+
+def gen_keys_ball(c0: KeyCollection, c1: KeyCollection, points: np.ndarray, ball: int, form: str = "bits",
+                  root_seeds=None, seed=None, seed_first: int = 0):
+    """The leader's `gen_l_inf_ball` (form "bits", ibDCF.rs:175-188) / `gen_l_inf_ball_from_coords` ("coords",
+    ibDCF.rs:189-205) for a population, on the GPU: server 0's keys into c0 and server 1's into c1 (both empty).
+    The bounds are computed in the keygen kernel from the packed points; the root seeds are `root_seeds` or, from
+    a 32-byte `seed`, the ChaCha20 block of (seed_first + client, dim): the same keys however the population is
+    cut into calls. A (seed, client index) pair must not be used twice."""
+    src, n, keep = _ball_src(points, ball, form, c0.n_dims, c0.depth, root_seeds, seed, seed_first)
+    check(lib().fhh_gen_keys_ball(c0.handle, c1.handle, n, ctypes.byref(src)), c0.handle)
+    del keep
+
+
 def sim_eq_count(c0: KeyCollection, c1: KeyCollection, C: int) -> np.ndarray:
     out = np.zeros(C, np.uint64)
     check(lib().fhh_sim_eq_count(c0.handle, c1.handle, ptr(out, u64p)), c0.handle)
@@ -516,4 +576,4 @@ def sim_ot_sums(c0: KeyCollection, c1: KeyCollection, C: int, prf_seed: int, las
     return [int(x) for x in a], [int(x) for x in b]
 
 
-__all__ = ["KeyCollection", "Result", "gen_keys_pair", "sim_eq_count", "sim_ot_sums", "FE_P", "FE255_P"]
+__all__ = ["KeyCollection", "Result", "gen_keys_pair", "gen_keys_ball", "ball_bounds", "sim_eq_count", "sim_ot_sums", "FE_P", "FE255_P"]

@@ -404,6 +404,11 @@ int group_add_keys_bincode_append(fhh_ctx* g, const uint8_t* req, uint64_t len);
 bool group_appended(const fhh_ctx* g);
 int group_gen_keys_pair(fhh_ctx* g0, fhh_ctx* g1, uint64_t n, const uint8_t* left, const uint8_t* right,
                         const uint8_t* roots);
+int group_gen_keys_ball(fhh_ctx* g0, fhh_ctx* g1, uint64_t n, const fhh_ball_src* src);
+// fhh_ball.cpp: fhh_gen_keys_ball on one-GPU ctxs (a carry out is named client_off + its index), and the refusals
+// of a source for a collection of d dims and L levels
+int gen_keys_ball_one(fhh_ctx* c0, fhh_ctx* c1, uint64_t n, const fhh_ball_src* src, uint64_t client_off);
+bool ball_src_check(uint32_t d, uint32_t L, uint64_t n, const fhh_ball_src* src, std::string* why);
 int group_num_clients(const fhh_ctx* g, uint64_t* n);
 int group_export_keys(fhh_ctx* g, uint8_t* key_idx, uint8_t* root_seed, uint8_t* cw_seed, uint8_t* cw_bits);
 int group_export_keys_bincode(fhh_ctx* g, uint64_t first, uint64_t count, uint64_t batch, uint8_t* out, uint64_t cap,

@@ -349,6 +349,39 @@ int group_gen_keys_pair(fhh_ctx* g0, fhh_ctx* g1, uint64_t n, const uint8_t* lef
     return FHH_OK;
 }
 
+// fhh_gen_keys_ball on multi-device ctxs: shard k keys its clients' points (fixed-size rows) and draws their root
+// seeds at seed_first + base[k], so the seed stream is the one-GPU collection's. Every shard looks for a carry out
+// among its own clients; the shards are reported in order, so the client named is the population's lowest.
+int group_gen_keys_ball(fhh_ctx* g0, fhh_ctx* g1, uint64_t n, const fhh_ball_src* src) {
+    if (!g0->group || !g1->group) return g0->fail(FHH_E_ARG, "gen_keys_ball: both ctxs must be multi-device ctxs");
+    Group &G0 = *g0->group, &G1 = *g1->group;
+    if (G0.devices != G1.devices || g0->d != g1->d || g0->L != g1->L)
+        return g0->fail(FHH_E_ARG, "gen_keys_ball: the two collections differ in devices / d / L");
+    if (G0.placed || G1.placed || g0->h_n || g1->h_n) return g0->fail(FHH_E_STATE, "gen_keys_ball: ctxs must be empty");
+    std::string why;
+    if (!ball_src_check(g0->d, g0->L, n, src, &why)) return g0->fail(FHH_E_ARG, "gen_keys_ball: " + why);
+    plan(G0, n);
+    plan(G1, n);
+    G0.reserved = G1.reserved = 0;
+    G0.placed = G1.placed = true;
+    const size_t row = (size_t)g0->d * (src->form == FHH_BALL_BITS ? (g0->L + 7) / 8 : 2), dR = (size_t)g0->d * 64;
+    const int rc = fan_out(g0, [&](size_t k, fhh_ctx* s) {
+        fhh_ball_src part = *src;
+        part.points = static_cast<const uint8_t*>(src->points) + G0.base[k] * row;
+        if (src->root_seeds) part.root_seeds = src->root_seeds + G0.base[k] * dR;
+        part.seed_first = src->seed_first + G0.base[k];
+        return gen_keys_ball_one(s, G1.shards[k], G0.count[k], &part, G0.base[k]);
+    });
+    if (rc) {
+        (void)group_reset(g0);
+        (void)group_reset(g1);
+        return rc;
+    }
+    set_bases(G0);
+    set_bases(G1);
+    return FHH_OK;
+}
+
 int group_num_clients(const fhh_ctx* g, uint64_t* n) {
     const Group& G = *g->group;
     uint64_t v = g->h_n;

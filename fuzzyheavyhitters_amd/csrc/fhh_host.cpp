@@ -810,7 +810,7 @@ int fhh_gen_keys_pair(fhh_ctx* c0, fhh_ctx* c1, uint64_t n, const uint8_t* left_
     HIP_TRY(c0, hipEventCreate(&e0));
     HIP_TRY(c0, hipEventCreate(&e1));
     HIP_TRY(c0, hipEventRecord(e0, c0->stream));
-    HIP_TRY(c0, launch_keygen(a, c0->stream));
+    HIP_TRY(c0, launch_keygen(a, kKeygenBytes, c0->stream));
     HIP_TRY(c0, hipEventRecord(e1, c0->stream));
     rc = ctx_sync(c0);
     float ms = 0.f;

@@ -288,16 +288,26 @@ struct PruneArgs {
     uint32_t ring32;            // r06, mode 1: the level's shares are in Z_2^32 (GcArgs::ring32): v0 - v1 mod 2^32
 };
 
+// k_keygen's sources of a key's bits (launch_keygen's `src`)
+constexpr int kKeygenBytes = 0;      // left_bits / right_bits, a byte per bit (fhh_gen_keys_pair)
+constexpr int kKeygenBallBits = 1;   // points: packed L-bit strings, the bounds a -/+ ball made in the kernel
+constexpr int kKeygenCoords = 2;     // points: i16 (lat, long), the clamped bounds made in the kernel (d = 2, L = 16)
 struct KeygenArgs {
     const uint8_t* left_bits;   // [n][d][L]
     const uint8_t* right_bits;
-    const uint8_t* root_seeds;  // [n][d][2 side][2 server][16]
+    const uint8_t* root_seeds;  // [n][d][2 side][2 server][16]; the point forms: NULL = drawn from `seed`
     uint4* cw_seed[2];
     uint64_t* cw_bits[2];
     uint4* root[2];
     uint64_t* key_idx[2];
     uint64_t n;
     uint32_t d, L, K, npad, nw;
+    // the point forms (fhh_gen_keys_ball, ball_src.h)
+    uint32_t ball;
+    const uint8_t* points;      // kKeygenBallBits: [n][d][ceil(L / 8)]; kKeygenCoords: int16 [n][2]
+    unsigned long long* bad;    // lowest c d + j whose right bound carries out of bit L (preset to ~0)
+    uint32_t seed[8];           // ChaCha20 key of the derived root seeds
+    uint64_t seed_first;        // global index of client 0 in the seed stream
 };
 
 // k_eval_paths (fhh_tree_init_at): every client's keys walked from the root to given prefixes. Job j = dim j's
@@ -345,7 +355,7 @@ hipError_t launch_child_sums_fe255(const ChildArgs& a, uint64_t* partials /*[C][
 // FE255 -> [C][8]
 hipError_t launch_sum_vals(const void* vals, uint32_t fmt, uint64_t C, uint64_t n, uint64_t ld, uint64_t* partials,
                            hipStream_t stream);
-hipError_t launch_keygen(const KeygenArgs& a, hipStream_t stream);
+hipError_t launch_keygen(const KeygenArgs& a, int src, hipStream_t stream);
 hipError_t launch_init_tables(const uint4* root, const uint64_t* key_idx, uint32_t dim, uint32_t K, uint32_t npad,
                               uint32_t nw, uint4* seed, uint64_t* t, uint64_t* y, hipStream_t stream);
 hipError_t launch_keys_from_aos(const uint8_t* key_idx, const uint8_t* root_seed, const uint8_t* cw_seed,

@@ -17,6 +17,7 @@
 #include "fhh_internal.h"
 #include "expand_kernel.h"
 #include "bincode_span.h"
+#include "ball_src.h"
 #include "../../include/fhh.h"
 // The measured-negative k_expand forms of r01-r03 (bitsliced VALU AES, the T-table + pair-sliced
 // hybrid, the earlier T-table variants) and their generated AES programs were removed in r06; they are
@@ -702,7 +703,18 @@ hipError_t launch_sum_vals(const void* vals, uint32_t fmt, uint64_t C, uint64_t 
 // k_keygen: one wave = 64 clients of one key (dim j, side). Restates gen_cor_word
 // (ibDCF.rs:84-119) level by level; 4 AES blocks per level per lane (both seeds, both
 // directions). Writes server 0's and server 1's key arrays (shared cor_words).
+// SRC = where the key's bits alpha come from (one body, as the FE / Z_2^32 table kernels share theirs):
+//   kKeygenBytes     the bounds as given, a byte per bit (fhh_gen_keys_pair)
+//   kKeygenBallBits  the client's packed L-bit point a: alpha = a -/+ ball (gen_l_inf_ball, ibDCF.rs:175-188)
+//   kKeygenCoords    the client's i16 (lat, long): alpha = clamp(c -/+ ball) (gen_l_inf_ball_from_coords, :189-205)
+// The point forms (ball_src.h) read the point once per item: its low word and the carry's run before the level
+// loop (ball_bound), then one 32-bit window per 32 levels; a level's bit comes from registers. A right bound that
+// carries out of bit L lowers *a.bad to its (client, dim) index c d + j; its key is made from the wrapped sum and
+// the host drops the whole call. With root_seeds = NULL the lane draws the 64 seed bytes of its (client, dim) as
+// one ChaCha20 block: the left and the right item of a (client, dim) each compute the block and keep their half
+// (~1 000 VALU ops beside an item's 4 L AES blocks; sharing it would cost a second pass or a pairing of items).
 // --------------------------------------------------------------------------------------
+template <int SRC>
 __global__ __launch_bounds__(kExpandThreads) void k_keygen(KeygenArgs a) {
     __shared__ uint32_t tbl[kTableWords];
     fill_table(tbl);
@@ -718,10 +730,38 @@ __global__ __launch_bounds__(kExpandThreads) void k_keygen(KeygenArgs a) {
         const uint32_t side = side_idx == 0 ? 1u : 0u;   // left key: side=true, right: false (ibDCF.rs:170-171)
         const uint64_t c = (uint64_t)w * 64 + lane;
         const bool valid = c < a.n;
-        const uint8_t* alpha = (side_idx == 0 ? a.left_bits : a.right_bits) + (valid ? (c * a.d + j) * a.L : 0);
+        const uint8_t* alpha = nullptr;   // kKeygenBytes: the bound; kKeygenBallBits: the point's row
+        BallBound bound{0u, 0xFFFFFFFFu, false};
+        uint32_t nb = 0, cur = 0;
+        if constexpr (SRC == kKeygenBytes) {
+            alpha = (side_idx == 0 ? a.left_bits : a.right_bits) + (valid ? (c * a.d + j) * a.L : 0);
+        } else if constexpr (SRC == kKeygenBallBits) {
+            nb = (a.L + 7) >> 3;
+            alpha = a.points + (valid ? (c * a.d + j) * nb : 0);
+            if (valid) {
+                bound = ball_bound(alpha, a.L, a.ball, side_idx == 1);
+                if (bound.carry_out) atomicMin(a.bad, (unsigned long long)(c * a.d + j));
+            }
+        } else {
+            // L = 16 < 32: every level reads bound.low (ball_bit)
+            if (valid) bound.low = coords_bound(reinterpret_cast<const int16_t*>(a.points)[c * 2 + j], j, a.ball, side_idx == 1);
+        }
 
         uint32_t seed[2][4];
-        if (valid) {
+        if (SRC != kKeygenBytes && !a.root_seeds && valid) {
+            uint32_t key[8], blk[16];
+#pragma unroll
+            for (int k = 0; k < 8; k++) key[k] = a.seed[k];
+            chacha20_block(key, (a.seed_first + c) * a.d + j, blk);
+            // words 0-7 (left) or 8-15 (right), picked by a mask: a ?: on the indices becomes a load from a
+            // stack copy of the block
+            const uint32_t right = 0u - side_idx;
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                seed[0][k] = blk[k] ^ ((blk[k] ^ blk[8 + k]) & right);
+                seed[1][k] = blk[4 + k] ^ ((blk[4 + k] ^ blk[12 + k]) & right);
+            }
+        } else if (valid) {
             const uint4* rs = reinterpret_cast<const uint4*>(a.root_seeds + ((c * a.d + j) * 2 + side_idx) * 32);
             const uint4 r0 = rs[0], r1 = rs[1];
             seed[0][0] = r0.x; seed[0][1] = r0.y; seed[0][2] = r0.z; seed[0][3] = r0.w;
@@ -742,7 +782,13 @@ __global__ __launch_bounds__(kExpandThreads) void k_keygen(KeygenArgs a) {
         uint32_t t[2] = {0u, 1u};                           // root_bits = (false, true), ibDCF.rs:140
 
         for (uint32_t l = 0; l < a.L; l++) {
-            const uint32_t bit = valid ? (alpha[l] ? 1u : 0u) : 0u;
+            uint32_t bit;
+            if constexpr (SRC == kKeygenBytes) {
+                bit = valid ? (alpha[l] ? 1u : 0u) : 0u;
+            } else {
+                if (SRC == kKeygenBallBits && valid && (l & 31) == 0 && l + 32 < a.L) cur = ball_str32(alpha, nb, l);
+                bit = valid ? ball_bit(bound, a.L, l, cur) : 0u;
+            }
             uint32_t blk[4][4];                             // index b*2 + dir
             uint32_t pbit[4], pyb[4];
 #pragma unroll
@@ -796,13 +842,26 @@ __global__ __launch_bounds__(kExpandThreads) void k_keygen(KeygenArgs a) {
     }
 }
 
-hipError_t launch_keygen(const KeygenArgs& a, hipStream_t stream) {
+hipError_t launch_keygen(const KeygenArgs& a, int src, hipStream_t stream) {
     const uint64_t items = (uint64_t)a.K * a.nw;
     if (items == 0) return hipSuccess;
     const uint64_t wpb = kExpandThreads / 64;
     uint64_t blocks = (items + wpb - 1) / wpb;
     if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(k_keygen, dim3((unsigned)blocks), dim3(kExpandThreads), 0, stream, a);
+    const dim3 grid((unsigned)blocks), block(kExpandThreads);
+    switch (src) {
+        case kKeygenBytes:
+            hipLaunchKernelGGL(k_keygen<kKeygenBytes>, grid, block, 0, stream, a);
+            break;
+        case kKeygenBallBits:
+            hipLaunchKernelGGL(k_keygen<kKeygenBallBits>, grid, block, 0, stream, a);
+            break;
+        case kKeygenCoords:
+            hipLaunchKernelGGL(k_keygen<kKeygenCoords>, grid, block, 0, stream, a);
+            break;
+        default:
+            return hipErrorInvalidValue;
+    }
     return hipGetLastError();
 }
 

@@ -71,6 +71,12 @@ def l_inf_ball_bounds(alpha: np.ndarray, ball: int):
     return _add_small(alpha, ball, -1), _add_small(alpha, ball, +1)
 
 
+def pack_points(alpha: np.ndarray) -> np.ndarray:
+    """Points as bits [n][d][L] (MSB first) -> the packed form `gen_keys_ball` takes: uint8 [n][d][ceil(L / 8)],
+    string bit l at bit 7 - l % 8 of byte l / 8; the pad bits of the last byte are 0."""
+    return np.packbits(np.ascontiguousarray(alpha, np.uint8), axis=-1, bitorder="big")
+
+
 def i16_to_bits(v: np.ndarray) -> np.ndarray:
     """sample_driving_data.rs:25-28: i16 -> 16 bits MSB first (two's complement)."""
     u = v.astype(np.int64) & 0xFFFF

@@ -120,6 +120,55 @@ int fhh_add_keys_bincode_append(fhh_ctx* ctx, const uint8_t* req, uint64_t len);
 int fhh_gen_keys_pair(fhh_ctx* ctx0, fhh_ctx* ctx1, uint64_t n, const uint8_t* left_bits,
                       const uint8_t* right_bits, const uint8_t* root_seeds);
 
+/* The leader's per-client step itself, from the points: `ibDCFKey::gen_l_inf_ball(point, ball_size)`
+ * (ibDCF.rs:175-188) as add_fuzzy_keys calls it for every client (leader.rs:130-163), and
+ * `gen_l_inf_ball_from_coords((lat, long), size)` (ibDCF.rs:189-205) for lat / long data. Both servers' keys are
+ * made on the GPU as by fhh_gen_keys_pair, with the interval bounds computed in the keygen kernel from the packed
+ * point and the root seeds drawn there, so a call moves the points and nothing else.
+ *
+ * FHH_BALL_BITS: the bounds of dim j are l = a - ball mod 2^L (subtract_bitstrings drops the carry, lib.rs:179: a
+ * wrapped interval, l > r, is keyed as the reference keys it) and r = a + ball. A carry out of bit L grows
+ * add_bitstrings' result (lib.rs:146-148) and the reference panics on `assert_eq!(left.len(), right.len())`
+ * (ibDCF.rs:182): here FHH_E_ARG, the message naming the lowest offending (client, dim). data_len < 32 is
+ * FHH_E_ARG: the reference pads the point to delta's 32 bits (lib.rs:132-134) and would make 32-level keys.
+ * FHH_BALL_COORDS: n_dims = 2, data_len = 16; the bounds are c -/+ ball in exact integers, clamped to +-9000
+ * (dim 0, lat) and +-18000 (dim 1, long) (ibDCF.rs:190-193), as 16 bits MSB first, two's complement
+ * (i16_to_bitvec, sample_driving_data.rs:25-28). The reference computes `lat - size` in i16, which a debug build
+ * panics on (and a release build wraps) past +-32767; that overflow is not reproduced: the exact value clamps.
+ *
+ * Root seeds: those given, or with root_seeds = NULL derived — the 64 bytes [side][server][16] of (client c, dim
+ * j) are the ChaCha20 block (RFC 8439 2.3, 20 rounds, 64-bit block counter, nonce 0) under key `seed` at counter
+ * (seed_first + c) n_dims + j. Keys therefore do not depend on how a population is cut into calls or shards. A
+ * (seed, client index) pair must be used once: a second use repeats root seeds, which is the caller's to avoid
+ * (a fresh seed per population, seed_first = the call's first client in it). */
+#define FHH_BALL_BITS   0  /* gen_l_inf_ball: points are L-bit strings                          */
+#define FHH_BALL_COORDS 1  /* gen_l_inf_ball_from_coords: points are int16 (lat, long), d=2, L=16 */
+typedef struct fhh_ball_src {
+    uint32_t form;
+    uint32_t ball;              /* delta; COORDS: <= 32767 */
+    const void* points;         /* host. BITS: uint8 [n][d][ceil(L/8)], MSB first: string bit l = bit 7-(l%8)
+                                   of byte l/8 (np.packbits, bitorder "big"); pad bits of the last byte ignored.
+                                   COORDS: int16 [n][2] = (lat, long) centidegrees */
+    const uint8_t* root_seeds;  /* host [n][d][2 side][2 server][16] as fhh_gen_keys_pair, or NULL: derive */
+    uint8_t seed[32];           /* used when root_seeds == NULL */
+    uint64_t seed_first;        /* global index of this call's client 0 in the seed stream */
+} fhh_ball_src;
+
+/* ctx0 / ctx1 as for fhh_gen_keys_pair: both empty (FHH_E_STATE otherwise), same device, n_dims and data_len;
+ * afterwards both hold their server's keys on the device and ctx0's stats.keygen_ms has the kernel's time. A
+ * refusal — a NULL pointer, an unknown form, a form that does not fit n_dims / data_len, a ball out of range, a
+ * carry out (found by the kernel, not by a host pass over the points) — leaves both ctxs empty and usable. On
+ * multi-device ctxs shard k keys its slice of the points with seed_first + its first client: the keys are those
+ * of a one-GPU collection. */
+int fhh_gen_keys_ball(fhh_ctx* ctx0, fhh_ctx* ctx1, uint64_t n, const fhh_ball_src* src);
+/* The host arithmetic of that call, no device call (like fhh_retain_plan / fhh_frontier_plan): the left_bits,
+ * right_bits [n][d][L] and root_seeds_out [n][d][2][2][16] that, handed to fhh_gen_keys_pair, give the keys of
+ * fhh_gen_keys_ball. Any output pointer may be NULL. *bad = the lowest c n_dims + j whose sum carries out,
+ * UINT64_MAX if none; a carry out returns FHH_E_ARG with nothing else written. The other refusals are those of
+ * fhh_gen_keys_ball's arguments. */
+int fhh_ball_bounds(uint32_t n_dims, uint32_t data_len, uint64_t n, const fhh_ball_src* src,
+                    uint8_t* left_bits, uint8_t* right_bits, uint8_t* root_seeds_out, uint64_t* bad);
+
 /* ---- one KeyCollection over several GPUs (north_star) -----------------------
  * KeyCollection::new on n_devices GPUs: one collection whose clients are sharded over the devices
  * (devices[k] may repeat — two shards on one GPU run the same code on a one-GPU box). At
