@@ -62,6 +62,7 @@ EXPORTS = [
     "fhh_retain_clients", "fhh_retain_plan", "fhh_retain_timing",
     "fhh_retain_clients_device", "fhh_retain_plan_device", "fhh_retain_mask_timing",
     "fhh_gen_keys_ball", "fhh_ball_bounds",
+    "fhh_party_set_server", "fhh_party_role_plan", "fhh_party_negate",
 ]
 
 
@@ -319,6 +320,9 @@ def lib():
         "fhh_ev_ot_shares": (i, [vp, vp, u64]),
         "fhh_party_node_sums": (i, [vp, vp, vp]),
         "fhh_party_bytes_sent": (i, [vp, u64p]),
+        "fhh_party_set_server": (i, [vp, i]),
+        "fhh_party_role_plan": (i, [u64, u64, u32, u32, u64, u64p, u64p, u64p, u8p]),
+        "fhh_party_negate": (i, [u32, vp, vp]),
         "fhh_gc_party_test_cfgs": (i, [u64, u32, P(FhhGbCfg), P(FhhEvCfg)]),
         "fhh_cot_extend_host": (i, [vp, u64, u32, u8p, u8p, u32, u8p, u8p, u64, u8p, u8p, u8p, u8p]),
         "fhh_cot_extend_ss_host": (i, [vp, u32, u64, u32, u8p, u8p, u32, u8p, u8p, u64, u8p, u8p, u8p, u8p, u8p]),

@@ -435,6 +435,24 @@ class KeyCollection:
     def reset(self):
         self._chk(lib().fhh_reset(self._h))
 
+    def party_set_server(self, server: int):
+        """Which server of the pair this collection is (0, 1; -1: unset, the default), until `reset`: with it
+        set, fhh_party_node_sums negates the sums of the children this server ran in the other server's usual
+        role, so that v0 - v1 is the count whoever garbled a child (a level split between the servers)."""
+        self._chk(lib().fhh_party_set_server(self._h, server))
+
+    @staticmethod
+    def party_role_plan(n_children: int, chunk_children: int, level: int, mode: int):
+        """[(begin, count, garbler)] of a level's windows (fhh_party_role_plan; mode 0 fixed, 1 swapped, 2 by
+        level, 3 split): the counts are the real ones, also for a one-window level."""
+        nw = ctypes.c_uint64(0)
+        check(lib().fhh_party_role_plan(n_children, chunk_children, level, mode, 0, ctypes.byref(nw), None, None, None))
+        W = nw.value
+        begin, count, garbler = np.zeros(W, np.uint64), np.zeros(W, np.uint64), np.zeros(W, np.uint8)
+        check(lib().fhh_party_role_plan(n_children, chunk_children, level, mode, W, ctypes.byref(nw), ptr(begin, u64p),
+                                        ptr(count, u64p), ptr(garbler)))
+        return [(int(b), int(c), int(g)) for b, c, g in zip(begin, count, garbler)]
+
     # ---- leader-side static helpers (collect.rs:945-1029) ------------------------------------
     @staticmethod
     def keep_values(nclients: int, threshold: int, vals0, vals1):

@@ -200,6 +200,7 @@ struct fhh_ctx {
     // this server's half of the current level's GC + OT when the two servers run on separate ctxs
     // (fhh_gb_* / fhh_ev_*, fhh_gcot.cpp)
     PartyState* party = nullptr;
+    int party_server = -1;   // fhh_party_set_server: which server of the pair this ctx is (-1 unset), until fhh_reset
 
     std::string err;
 

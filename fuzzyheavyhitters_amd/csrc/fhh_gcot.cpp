@@ -305,18 +305,17 @@ int fhh_ot_extend_device(fhh_ctx* ctx, const fhh_ot_batch* b) {
 namespace fhh {
 namespace eng {
 
-struct PartyState {
-    int role = -1;              // 0 garbler / OT sender (server 0), 1 evaluator / OT receiver (server 1)
+// one protocol instance of a ctx: the garbler's (fhh_gb_*) or the evaluator's (fhh_ev_*), with the chunk it is
+// running, its buffers and its role's base-OT sessions
+struct PartyInst {
     int step = 0;               // protocol position (calls must come in order)
+    bool busy = false;          // a chunk of the level is open in this instance (labels OT done, share step not yet)
     bool last = false;          // tree_crawl_last: FieldElm shares (BlockPair = 2 OTs per test)
     // the chunk's form (gt_plan.h, set by party_begin): tile_major at b <= 2 only; nw_gc / npad_gc serve both parties
     GtPlan plan{};
     // C = this instance's children: the chunk [c_off, c_off + C) of the level's level_C children
-    // (child_begin / child_count); covered = children whose OTs are finished
-    uint64_t c_off = 0, level_C = 0, covered = 0;
-    uint32_t level_id = 0;
-    bool level_last = false;
-    uint32_t level_form = 0;    // the level's first chunk's form: its storage (partials or vals) serves every chunk
+    // (child_begin / child_count)
+    uint64_t c_off = 0;
     uint64_t C = 0, n = 0, tests = 0, m1 = 0, m2 = 0;
     uint32_t bits = 0, mask = 0;
     uint32_t s[2][4] = {};      // garbler: the OT-extension sender's base choice words per OT kind
@@ -332,16 +331,35 @@ struct PartyState {
     DevBuf T, U, Q, Y;          // OT matrices (T / Q private) and messages (U or y)
     DevBuf choices2;            // evaluator: the GC outputs packed as OT 2's choice words
     DevBuf out;                 // evaluator: GC output bytes (eq ^ mask)
-    DevBuf vals;                // the level's node values [level_C][n] (u64, u32 with ring32, or a BlockPair at the last level)
-    DevBuf ring_sums;           // ring32 without fused_sums: the per-child u64 totals of vals (k_ring32_child_sums)
     std::vector<uint32_t> rk_host;
-    uint64_t bytes_sent = 0;    // this ctx's outgoing message bytes for the level
+    uint64_t bytes_sent = 0;    // this instance's outgoing message bytes for the level
     uint32_t ss_k = 1;          // r06: 1 IKNP, 2 / 4 SoftSpoken (both OT kinds; fhh_ev_cfg / fhh_gb_cfg.ot_ss_k)
     DevBuf ss_leaf;             // SoftSpoken: this party's GGM leaves
+};
+
+// a ctx's two instances (in[0] the garbler, in[1] the evaluator) and the level they share: a level's chunks may
+// run in either role (a split level), so the level's storage belongs to neither instance and is set up by the
+// level's first chunk, whichever role opens it
+struct PartyState {
+    PartyInst in[2];
+    bool began = false;         // a level was opened (child_begin = 0) and the fields below describe it
+    uint64_t level_C = 0;
+    uint32_t level_id = 0;
+    bool level_last = false;
+    uint32_t level_form = 0;    // the level's first chunk's form: its storage (partials or vals) serves every chunk
+    GtPlan plan{};              // the level's plan (the first chunk's: fused_sums, ring32 and per2 do not change in a level)
+    uint64_t n = 0;
+    // opened = where the last chunk opened in the level ends (the next chunk begins there, in either role);
+    // covered = where the last finished chunk ends; finished = the children of all finished chunks; chunks = their number
+    uint64_t opened = 0, covered = 0, finished = 0, chunks = 0;
+    std::vector<uint8_t> child_role;   // [level_C]: the role this ctx ran child c in (0 garbled it, 1 evaluated it)
+    DevBuf vals;                // the level's node values [level_C][n] (u64, u32 with ring32, or a BlockPair at the last level)
+    DevBuf ring_sums;           // ring32 without fused_sums: the per-child u64 totals of vals (k_ring32_child_sums)
     // r06 (plan.fused_sums): the table kernels add this party's node values per child into partials [level_C][4]
     // (the level loop's layout: garbler slots 0, 1, evaluator 2, 3) instead of storing them in vals, and the
     // garble / evaluate calls copy the partials to the host before they return: fhh_party_node_sums then
-    // needs no device work (no sums kernel, no values round trip, no extra synchronisation)
+    // needs no device work (no sums kernel, no values round trip, no extra synchronisation). The instances'
+    // children are disjoint and the partials start at zero, so a child's total is the sum of both slot pairs
     DevBuf partials;
     std::vector<uint64_t> partials_host;
 };
@@ -369,7 +387,8 @@ int party_begin(fhh_ctx* ctx, int role, uint64_t child_begin, uint64_t child_cou
     if (form == 2 && 2 * ctx->d > (uint32_t)kGtMaxBits)
         return ctx->fail(FHH_E_ARG, "party: form 2 (the garbled table with Z_2^32 shares) needs 2d <= 4; there is no "
                                     "ring form of the circuit");
-    PartyState& P = party_of(ctx);
+    PartyState& S = party_of(ctx);
+    PartyInst& P = S.in[role];
     const bool last = ctx->phase == Phase::kPendingLast;
     // the chunk of children (collect.rs:423-430: a level's tests split over channels), in order
     const uint64_t LC = ctx->pending_C, b = child_begin;
@@ -377,22 +396,33 @@ int party_begin(fhh_ctx* ctx, int role, uint64_t child_begin, uint64_t child_cou
     if (b > LC || (child_count && b == LC && LC))
         return ctx->fail(FHH_E_ARG, "party: child_begin " + std::to_string(b) + " past the level's " +
                                         std::to_string(LC) + " children");
-    if (b != 0 && (P.role != role || P.level_id != ctx->level || P.level_last != last || P.level_C != LC ||
-                   P.covered != b))
+    // a follow-on chunk begins where the last chunk opened in this level ended, in either role, and the instance
+    // it reuses has finished its own previous chunk (in one role throughout: covered == child_begin)
+    if (b != 0 && (!S.began || S.level_id != ctx->level || S.level_last != last || S.level_C != LC || S.opened != b ||
+                   P.busy))
         return ctx->fail(FHH_E_STATE, "party: chunk at child " + std::to_string(b) + " does not follow the level's " +
-                                          "finished children (" + std::to_string(P.covered) + ")");
+                                          "finished children (" + std::to_string(S.covered) + ")");
     // the level's storage (the fused partials or vals) follows the form and is set up by the first chunk only
-    if (b != 0 && P.level_form != form)
+    if (b != 0 && S.level_form != form)
         return ctx->fail(FHH_E_STATE, "party: chunk at child " + std::to_string(b) + " has form " + std::to_string(form) +
-                                          ", the level's first chunk had form " + std::to_string(P.level_form));
-    P.role = role;
+                                          ", the level's first chunk had form " + std::to_string(S.level_form));
+    if (b == 0) {   // a new level: both instances start over (a chunk the other role left open is dropped)
+        S.began = true;
+        S.level_form = form;
+        S.level_id = ctx->level;
+        S.level_last = last;
+        S.level_C = LC;
+        S.n = ctx->n;
+        S.opened = S.covered = S.finished = S.chunks = 0;
+        S.child_role.assign(LC, 0);
+        for (PartyInst& I : S.in) {
+            I.step = 0;
+            I.busy = false;
+            I.bytes_sent = 0;   // the level's outgoing bytes, over its chunks
+        }
+    }
     P.step = 0;
     P.last = last;
-    if (b == 0) P.level_form = form;
-    P.level_id = ctx->level;
-    P.level_last = last;
-    P.level_C = LC;
-    if (b == 0) P.covered = 0;
     P.c_off = b;
     P.C = child_count ? std::min<uint64_t>(child_count, LC - b) : LC;
     P.n = ctx->n;
@@ -403,7 +433,7 @@ int party_begin(fhh_ctx* ctx, int role, uint64_t child_begin, uint64_t child_cou
     P.plan = ctx_gt_plan(ctx, GtCaller::kParty, P.bits, last ? 2 : 1, form == 1 ? 3 : 2, form == 2, ctx->nw);
     P.m1 =P.C * P.bits * P.plan.npad_gc;   // OT index (g bits + j) npad + i: the share planes as choice bits
     P.m2 = P.plan.lshare ? 0 : P.tests * P.plan.per2;   // OT 2 (the share OT) at the FieldElm level only
-    if (b == 0) P.bytes_sent = 0;   // the level's outgoing bytes, over its chunks
+    if (b == 0) S.plan = P.plan;
     // this server's share planes [C][bits][nw] of the chunk (collect.rs:393-418), zero-padded to the
     // OT's whole choice words (ot_padded(m1) bits)
     const uint64_t plane_words = P.C * P.bits * P.plan.nw_gc, pad_words = ot_padded(std::max<uint64_t>(P.m1, 1)) / 64;
@@ -419,27 +449,51 @@ int party_begin(fhh_ctx* ctx, int role, uint64_t child_begin, uint64_t child_cou
     // the level's node values, one row of n per child (u64 FE, or a BlockPair at the last level); with the
     // fused sums (tile_major) only the per-child partials, zeroed at the level's first chunk
     if (b == 0 && P.plan.fused_sums) {
-        HIP_TRY(ctx, P.partials.ensure(std::max<uint64_t>(LC, 1) * 4 * 8));
-        HIP_TRY(ctx, hipMemsetAsync(P.partials.p, 0, std::max<uint64_t>(LC, 1) * 4 * 8, ctx->stream));
-        P.partials_host.assign(std::max<uint64_t>(LC, 1) * 4, 0);
+        HIP_TRY(ctx, S.partials.ensure(std::max<uint64_t>(LC, 1) * 4 * 8));
+        HIP_TRY(ctx, hipMemsetAsync(S.partials.p, 0, std::max<uint64_t>(LC, 1) * 4 * 8, ctx->stream));
+        S.partials_host.assign(std::max<uint64_t>(LC, 1) * 4, 0);
     } else if (b == 0) {
-        HIP_TRY(ctx, P.vals.ensure(std::max<uint64_t>(LC * P.n * P.plan.per2, 1) * (P.last ? 16 : P.plan.ring32 ? 4 : 8)));
+        HIP_TRY(ctx, S.vals.ensure(std::max<uint64_t>(LC * P.n * P.plan.per2, 1) * (P.last ? 16 : P.plan.ring32 ? 4 : 8)));
     }
     return FHH_OK;
 }
 
+// the chunk is open (its labels OT is done): the level's next chunk begins where it ends. Recorded only now, so
+// a *_ot_labels call that was refused after party_begin (a wrong U size) leaves the chunk to be opened again
+void party_opened(PartyState& S, PartyInst& P, int role) {
+    P.step = 1;
+    P.busy = true;
+    S.opened = P.c_off + P.C;
+    std::fill(S.child_role.begin() + P.c_off, S.child_role.begin() + P.c_off + P.C, (uint8_t)role);
+}
+
+// the chunk's share step is done: its children are covered
+void party_finished(PartyState& S, PartyInst& P) {
+    P.step = 3;
+    P.busy = false;
+    S.covered = std::max(S.covered, P.c_off + P.C);
+    S.finished += P.C;
+    S.chunks++;
+}
+
+// the finished chunks of both instances cover [0, level_C) exactly (chunks open back to back, so they cannot
+// overlap: every opened one finished and the last one ends the level)
+bool party_level_done(const PartyState& S) {
+    return S.began && S.chunks && !S.in[0].busy && !S.in[1].busy && S.opened == S.level_C && S.finished == S.level_C;
+}
+
 // the fused partials of the level so far, to the host (each chunk's call copies the whole accumulating
 // array; after the level's last chunk the host copy is complete)
-int party_partials_to_host(fhh_ctx* ctx, PartyState& P) {
-    if (!P.plan.fused_sums || P.level_C == 0) return FHH_OK;
-    HIP_TRY(ctx, hipMemcpyAsync(P.partials_host.data(), P.partials.p, P.level_C * 4 * 8, hipMemcpyDeviceToHost,
+int party_partials_to_host(fhh_ctx* ctx, PartyState& S) {
+    if (!S.plan.fused_sums || S.level_C == 0) return FHH_OK;
+    HIP_TRY(ctx, hipMemcpyAsync(S.partials_host.data(), S.partials.p, S.level_C * 4 * 8, hipMemcpyDeviceToHost,
                                 ctx->stream));
     return FHH_OK;
 }
 
 // base-OT session of OT kind w: the same material as the running session continues its counter,
 // new material starts a session at 0; the chunk's m OTs take the next blocks
-void party_session(PartyState& P, int w, const uint8_t* mat, size_t bytes, uint64_t m) {
+void party_session(PartyInst& P, int w, const uint8_t* mat, size_t bytes, uint64_t m) {
     if (P.sess[w].size() != bytes || std::memcmp(P.sess[w].data(), mat, bytes) != 0) {
         P.sess[w].assign(mat, mat + bytes);
         P.sess_next[w] = 0;
@@ -450,7 +504,7 @@ void party_session(PartyState& P, int w, const uint8_t* mat, size_t bytes, uint6
 
 // key schedules of OT kind w's base OTs into P.rk[w]: receiver rows 0 / 1 from both seeds of each
 // base OT, sender row 2 from its chosen seeds (the other party's rows stay zero: never read)
-int party_keys(fhh_ctx* ctx, PartyState& P, int w, const uint8_t* pairs /*[128][2][16] or null*/,
+int party_keys(fhh_ctx* ctx, PartyInst& P, int w, const uint8_t* pairs /*[128][2][16] or null*/,
                const uint8_t* chosen /*[128][16] or null*/) {
     P.rk_host.resize((size_t)3 * 128 * 44);
     base_ot_schedules(pairs, chosen, P.rk_host.data());
@@ -461,7 +515,7 @@ int party_keys(fhh_ctx* ctx, PartyState& P, int w, const uint8_t* pairs /*[128][
     return FHH_OK;
 }
 
-OtArgs party_ot(PartyState& P, int w, uint64_t m) {
+OtArgs party_ot(PartyInst& P, int w, uint64_t m) {
     OtArgs a{};
     a.m = m;
     a.mp = ot_padded(m);
@@ -476,7 +530,7 @@ OtArgs party_ot(PartyState& P, int w, uint64_t m) {
 
 // SoftSpoken (P.ss_k > 1): this party's half of the GGM trees before its expand — the receiver's corrections
 // go after U in its message, the sender reads them there (a.U = the received message)
-hipError_t party_ggm(PartyState& P, OtArgs& a, bool receiver, hipStream_t stream) {
+hipError_t party_ggm(PartyInst& P, OtArgs& a, bool receiver, hipStream_t stream) {
     if (P.ss_k < 2) return hipSuccess;
     a.ss_leaf = P.ss_leaf.as<uint4>();
     a.ss_corr = reinterpret_cast<uint4*>(reinterpret_cast<uint8_t*>(a.U) + 16 * a.mp / P.ss_k);
@@ -487,7 +541,7 @@ hipError_t party_ggm(PartyState& P, OtArgs& a, bool receiver, hipStream_t stream
 // message sizes: U = 128 / k rows of the padded OTs (+ SoftSpoken's GGM corrections, 4 KiB)
 uint64_t u_bytes(uint64_t m, uint32_t k) { return 16 * ot_padded(m) / k + (k > 1 ? 128 * 2 * 16 : 0); }
 
-int party_ot_buffers(fhh_ctx* ctx, PartyState& P, uint64_t m, bool receiver, bool reply = true) {
+int party_ot_buffers(fhh_ctx* ctx, PartyInst& P, uint64_t m, bool receiver, bool reply = true) {
     const uint64_t rows = 16 * ot_padded(m);   // [128][mp / 128] blocks
     HIP_TRY(ctx, (receiver ? P.T : P.Q).ensure(rows));
     if (receiver) HIP_TRY(ctx, P.U.ensure(u_bytes(m, P.ss_k)));
@@ -496,11 +550,11 @@ int party_ot_buffers(fhh_ctx* ctx, PartyState& P, uint64_t m, bool receiver, boo
     return FHH_OK;
 }
 
-uint64_t gc_bytes(const PartyState& P) {
+uint64_t gc_bytes(const PartyInst& P) {
     if (P.plan.table) return P.tests * (((uint64_t)1 << P.bits) - 1) * (P.plan.ring32 ? 4 : 8);   // rows 1 .. 2^bits - 1, 8 B (Z_2^32: 4 B) each
     return P.tests * ((uint64_t)2 * (P.bits - 1) * 16 + 1 + (P.plan.lshare ? 8 : 0));
 }
-uint64_t y2_bytes(const PartyState& P) { return P.m2 * (P.last ? 16 : 8); }
+uint64_t y2_bytes(const PartyInst& P) { return P.m2 * (P.last ? 16 : 8); }
 
 int check_in(fhh_ctx* ctx, const void* p, uint64_t got, uint64_t want, const char* what) {
     if (want && !p) return ctx->fail(FHH_E_ARG, std::string("party: NULL ") + what);
@@ -512,7 +566,7 @@ int check_in(fhh_ctx* ctx, const void* p, uint64_t got, uint64_t want, const cha
 
 // carve the gc message [tables | y | decode] (the garbler's string and mask are folded into the circuit:
 // no garbler labels cross, k_gc_garble_cot; y = the FE share's 8 B per test at the FE levels, r05c)
-void gc_layout(const PartyState& P, uint8_t* base, GcArgs& g) {
+void gc_layout(const PartyInst& P, uint8_t* base, GcArgs& g) {
     const uint64_t t = P.tests, tb = (uint64_t)2 * (P.bits - 1) * t * 16;
     g.tables = reinterpret_cast<uint4*>(base);
     g.gb_labels = nullptr;
@@ -527,27 +581,28 @@ void gc_layout(const PartyState& P, uint8_t* base, GcArgs& g) {
 }
 
 // this chunk's rows of the level's node values (u64 FE, u32 in Z_2^32, or a BlockPair at the last level)
-uint8_t* party_vals(PartyState& P) {
-    return P.vals.as<uint8_t>() + P.c_off * P.n * P.plan.per2 * (P.last ? 16 : P.plan.ring32 ? 4 : 8);
+uint8_t* party_vals(PartyState& S, PartyInst& P) {
+    return S.vals.as<uint8_t>() + P.c_off * P.n * P.plan.per2 * (P.last ? 16 : P.plan.ring32 ? 4 : 8);
 }
 
 // form 2: this ctx's per-child totals of the level's Z_2^32 node values, added into acc [level_C] (u64; the
-// caller reduces mod 2^32 once): the fused partials' low sums (b <= 2), or k_ring32_child_sums over vals
-int party_ring_totals(fhh_ctx* ctx, PartyState& P, std::vector<uint64_t>& acc) {
-    const uint64_t LC = P.level_C;
-    if (P.plan.fused_sums) {
-        const int k0 = P.role == 0 ? 0 : 2;
-        for (uint64_t c = 0; c < LC; c++) acc[c] += P.partials_host[4 * c + k0] + (P.partials_host[4 * c + k0 + 1] << 32);
+// caller reduces mod 2^32 once): the fused partials' low sums (b <= 2; both slot pairs: a child's other pair is
+// zero), or k_ring32_child_sums over vals
+int party_ring_totals(fhh_ctx* ctx, PartyState& S, std::vector<uint64_t>& acc) {
+    const uint64_t LC = S.level_C;
+    if (S.plan.fused_sums) {
+        const std::vector<uint64_t>& h = S.partials_host;
+        for (uint64_t c = 0; c < LC; c++) acc[c] += h[4 * c] + h[4 * c + 2] + ((h[4 * c + 1] + h[4 * c + 3]) << 32);
         return FHH_OK;
     }
     if (LC == 0) return FHH_OK;
     int rc = ctx_set_device(ctx);
     if (rc) return rc;
-    HIP_TRY(ctx, P.ring_sums.ensure(LC * 8));
-    HIP_TRY(ctx, hipMemsetAsync(P.ring_sums.p, 0, LC * 8, ctx->stream));
-    HIP_TRY(ctx, launch_ring32_child_sums(P.vals.as<uint32_t>(), P.n, LC, P.ring_sums.as<uint64_t>(), ctx->stream));
+    HIP_TRY(ctx, S.ring_sums.ensure(LC * 8));
+    HIP_TRY(ctx, hipMemsetAsync(S.ring_sums.p, 0, LC * 8, ctx->stream));
+    HIP_TRY(ctx, launch_ring32_child_sums(S.vals.as<uint32_t>(), S.n, LC, S.ring_sums.as<uint64_t>(), ctx->stream));
     std::vector<uint64_t> h(LC);
-    HIP_TRY(ctx, hipMemcpyAsync(h.data(), P.ring_sums.p, LC * 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(h.data(), S.ring_sums.p, LC * 8, hipMemcpyDeviceToHost, ctx->stream));
     rc = ctx_sync(ctx);
     if (rc) return rc;
     for (uint64_t c = 0; c < LC; c++) acc[c] += h[c];
@@ -556,13 +611,139 @@ int party_ring_totals(fhh_ctx* ctx, PartyState& P, std::vector<uint64_t>& acc) {
 
 // the chunk's gate tweaks: the level in bits 40+ (Delta = the labels session's s may serve several levels
 // when base OTs are reused), then the test's index in the whole level (c_off n + t)
-uint64_t party_gate_base(const PartyState& P) { return ((uint64_t)P.level_id << 40) + P.c_off * P.n * (P.bits - 1); }
+uint64_t party_gate_base(const PartyState& S, const PartyInst& P) {
+    return ((uint64_t)S.level_id << 40) + P.c_off * P.n * (P.bits - 1);
+}
+
+// ---- the sign of the node sums (fhh_party_set_server) ----------------------------------------------
+// The shares come out as garbler - evaluator = eq. With the ctx's server set, a child this ctx ran in the other
+// server's usual role (server 0 evaluated it, or server 1 garbled it) has its sum negated, so that v0 - v1 is the
+// count for every child whoever garbled it. Host arithmetic on the per-child sums.
+uint64_t fe_negate(uint64_t s) { return s ? kFieldFeP - s : 0; }
+uint64_t ring32_negate(uint64_t s) { return (0 - s) & 0xFFFFFFFFull; }
+// x (10 limbs, unreduced) -> -x mod 2^255 - 19, canonical
+void fe255_negate(const uint32_t* x10, uint32_t* out8) {
+    uint32_t r[8];
+    const uint32_t zero[8] = {};
+    fhh::fe255_reduce(x10, r);
+    fhh::fe255_sub(zero, r, out8);
+}
+
+// neg[c] = 1 where child c's sum is negated. Server unset: nothing is, and a level whose chunks mixed roles is
+// refused (its sums would carry both signs)
+int party_sign_flags(fhh_ctx* ctx, const PartyState& S, int server, std::vector<uint8_t>& neg) {
+    neg.assign(S.level_C, 0);
+    if (server < 0) {
+        for (uint64_t c = 1; c < S.level_C; c++)
+            if (S.child_role[c] != S.child_role[0])
+                return ctx->fail(FHH_E_STATE, "party_node_sums: the level's chunks ran in both roles; say which server "
+                                              "this ctx is first (fhh_party_set_server)");
+        return FHH_OK;
+    }
+    for (uint64_t c = 0; c < S.level_C; c++) neg[c] = S.child_role[c] != (uint8_t)server;
+    return FHH_OK;
+}
+
+// the FieldElm level's negated children: the unreduced output and the recorded last_values entry (what
+// fhh_final_shares hands out) both become the canonical negated value, zero-extended
+void party_negate_last(const std::vector<fhh_ctx*>& owners, const std::vector<uint8_t>& neg, uint32_t* unr, uint32_t* can) {
+    if (owners.empty()) return;
+    for (uint64_t c = 0; c < neg.size() && c < owners[0]->last_values.size(); c++) {
+        if (!neg[c]) continue;
+        Limbs10 v{};
+        fe255_negate(owners[0]->last_values[c].data(), v.data());
+        if (unr) std::memcpy(unr + c * 10, v.data(), 40);
+        if (can) std::memcpy(can + c * 8, v.data(), 32);
+        for (fhh_ctx* o : owners)
+            if (c < o->last_values.size()) o->last_values[c] = v;
+    }
+}
 
 }  // namespace
 }  // namespace eng
 }  // namespace fhh
 
 extern "C" {
+
+// ---- which server this ctx is, the roles of a level's windows, the negation itself (host) ------------
+int fhh_party_set_server(fhh_ctx* ctx, int server) {
+    CTX_CHECK(ctx);
+    if (server < -1 || server > 1) return ctx->fail(FHH_E_ARG, "party_set_server: server must be 0, 1 or -1 (unset)");
+    std::vector<fhh_ctx*> all;
+    if (ctx->group) {
+        int S = 0;
+        int rc = fhh_shard_info(ctx, 0, &S, nullptr, nullptr, nullptr, nullptr);
+        if (rc) return rc;
+        for (int k = 0; k < S; k++) {
+            fhh_ctx* sh = nullptr;
+            rc = fhh_shard_ctx(ctx, k, &sh);
+            if (rc) return rc;
+            all.push_back(sh);
+        }
+    } else {
+        all.push_back(ctx);
+    }
+    for (fhh_ctx* c : all) {
+        const PartyState* S = c->party;
+        // open: the pending crawl's level has begun and its chunks do not cover it yet (a level abandoned before a
+        // new tree_init or crawl is not: its first chunk starts it over)
+        const bool pending = c->phase == Phase::kPending || c->phase == Phase::kPendingLast;
+        if (S && pending && S->began && S->level_id == c->level && S->level_C == c->pending_C && !party_level_done(*S))
+            return ctx->fail(FHH_E_STATE, "party_set_server: a level's protocol is open (finish its chunks first)");
+    }
+    for (fhh_ctx* c : all) c->party_server = server;
+    ctx->party_server = server;
+    return FHH_OK;
+}
+
+int fhh_party_role_plan(uint64_t n_children, uint64_t chunk_children, uint32_t level, uint32_t mode, uint64_t cap,
+                        uint64_t* n_windows, uint64_t* begin, uint64_t* count, uint8_t* garbler) {
+    auto refuse = [](const char* m) {
+        g_err = std::string("party_role_plan: ") + m;
+        return FHH_E_ARG;
+    };
+    if (mode > 3) return refuse("mode must be 0 (fixed), 1 (swapped), 2 (by level) or 3 (split)");
+    if (!n_windows) return refuse("NULL n_windows");
+    const bool query = !begin && !count && !garbler;   // the window count alone
+    if (!query && (!begin || !count || !garbler)) return refuse("begin, count and garbler go together");
+    const uint64_t C = n_children;
+    // today's windows: chunks of chunk_children (0, or a level that fits one chunk: the whole level)
+    uint64_t step = chunk_children && C > chunk_children ? chunk_children : C;
+    // a split level of one window is cut in two, so that both servers garble
+    if (mode == 3 && step == C && C >= 2) step = (C + 1) / 2;
+    const uint64_t W = step ? (C + step - 1) / step : 1;
+    *n_windows = W;
+    if (query) return FHH_OK;
+    if (cap < W) return refuse("cap is smaller than the number of windows");
+    for (uint64_t w = 0; w < W; w++) {
+        begin[w] = w * step;
+        count[w] = std::min<uint64_t>(step, C - w * step);
+        garbler[w] = mode == 0 ? 0 : mode == 1 ? 1 : mode == 2 ? (level & 1) : (uint8_t)((level + w) & 1);
+    }
+    return FHH_OK;
+}
+
+int fhh_party_negate(uint32_t fmt, const void* in, void* out) {
+    if (fmt > 2 || !in || !out) {
+        g_err = "party_negate: fmt must be 0 (FE), 1 (Z_2^32) or 2 (FieldElm), with both buffers";
+        return FHH_E_ARG;
+    }
+    if (fmt == 2) {
+        fe255_negate(static_cast<const uint32_t*>(in), static_cast<uint32_t*>(out));
+        return FHH_OK;
+    }
+    const uint64_t s = *static_cast<const uint64_t*>(in);
+    if (fmt == 0 && s >= fhh::kFieldFeP) {
+        g_err = "party_negate: the FE value is not canonical";
+        return FHH_E_ARG;
+    }
+    if (fmt == 1 && s >> 32) {
+        g_err = "party_negate: the Z_2^32 value is not zero-extended";
+        return FHH_E_ARG;
+    }
+    *static_cast<uint64_t*>(out) = fmt == 0 ? fe_negate(s) : ring32_negate(s);
+    return FHH_OK;
+}
 
 int fhh_ev_ot_labels(fhh_ctx* ctx, const fhh_ev_cfg* cfg, const uint8_t** u_dev, uint64_t* u_len) {
     CTX_CHECK(ctx);
@@ -573,7 +754,8 @@ int fhh_ev_ot_labels(fhh_ctx* ctx, const fhh_ev_cfg* cfg, const uint8_t** u_dev,
         return ctx->fail(FHH_E_ARG, "ev_ot_labels: ot_ss_k must be 0 / 1 (IKNP), 2 or 4 (SoftSpoken)");
     int rc = party_begin(ctx, 1, cfg->child_begin, cfg->child_count, cfg->form);
     if (rc) return rc;
-    PartyState& P = *ctx->party;
+    PartyState& S = *ctx->party;
+    PartyInst& P = S.in[1];
     P.ss_k = cfg->ot_ss_k > 1 ? cfg->ot_ss_k : 1;
     // both OT kinds' receiver schedules and session counters (OtReceiver::init, collect.rs:460)
     // (kind 1, the share OT, at the FieldElm level only: the FE levels' share rides on the GC, r05c)
@@ -599,7 +781,7 @@ int fhh_ev_ot_labels(fhh_ctx* ctx, const fhh_ev_cfg* cfg, const uint8_t** u_dev,
     }
     rc = ctx_sync(ctx);
     if (rc) return rc;
-    P.step = 1;
+    party_opened(S, P, 1);
     *u_dev = P.U.as<uint8_t>();
     *u_len = P.m1 ? u_bytes(P.m1, P.ss_k) : 0;
     P.bytes_sent += *u_len;
@@ -616,7 +798,8 @@ int fhh_gb_ot_labels(fhh_ctx* ctx, const fhh_gb_cfg* cfg, const uint8_t* u_dev, 
         return ctx->fail(FHH_E_ARG, "gb_ot_labels: ot_ss_k must be 0 / 1 (IKNP), 2 or 4 (SoftSpoken)");
     int rc = party_begin(ctx, 0, cfg->child_begin, cfg->child_count, cfg->form);
     if (rc) return rc;
-    PartyState& P = *ctx->party;
+    PartyState& S = *ctx->party;
+    PartyInst& P = S.in[0];
     P.ss_k = cfg->ot_ss_k > 1 ? cfg->ot_ss_k : 1;
     rc = check_in(ctx, u_dev, u_len, P.m1 ? u_bytes(P.m1, P.ss_k) : 0, "U (labels OT)");
     if (rc) return rc;
@@ -647,7 +830,7 @@ int fhh_gb_ot_labels(fhh_ctx* ctx, const fhh_gb_cfg* cfg, const uint8_t* u_dev, 
     gb.bits = P.bits;
     gb.mask = P.mask;
     std::memcpy(gb.delta, cfg->base_choice[0], 16);   // Delta = the labels session's s
-    gb.gate_base = party_gate_base(P);
+    gb.gate_base = party_gate_base(S, P);
     gb.gb_planes_dev = P.planes.as<uint64_t>();
     gb.ev_planes_dev = P.planes.as<uint64_t>();   // not read: the evaluator's labels go by OT
     gb.tables_dev = P.gc.as<uint8_t>();
@@ -664,8 +847,8 @@ int fhh_gb_ot_labels(fhh_ctx* ctx, const fhh_gb_cfg* cfg, const uint8_t* u_dev, 
     P.g.out = nullptr;
     // r05c: the garbler's node values r1 straight into the level's rows (the y it forms travels in gc);
     // r06 (tile_major): added per child into the partials instead
-    P.g.sh_gb = P.plan.lshare && !P.plan.fused_sums ? reinterpret_cast<uint64_t*>(party_vals(P)) : nullptr;
-    P.g.node_partials = P.plan.fused_sums ? P.partials.as<uint64_t>() : nullptr;
+    P.g.sh_gb = P.plan.lshare && !P.plan.fused_sums ? reinterpret_cast<uint64_t*>(party_vals(S, P)) : nullptr;
+    P.g.node_partials = P.plan.fused_sums ? S.partials.as<uint64_t>() : nullptr;
     P.g.node_off = P.c_off;
     // OT 1 as the IKNP correlation (gb_set_fancy_inputs, equalitytest.rs:67-82): q_j is the evaluator's
     // zero label of its share bit j, q_j ^ s its one label, and s = Delta: nothing to send back
@@ -682,7 +865,7 @@ int fhh_gb_ot_labels(fhh_ctx* ctx, const fhh_gb_cfg* cfg, const uint8_t* u_dev, 
     }
     rc = ctx_sync(ctx);
     if (rc) return rc;
-    P.step = 1;
+    party_opened(S, P, 0);
     *y_dev = nullptr;
     *y_len = 0;   // the labels OT has no reply
     return FHH_OK;
@@ -693,13 +876,13 @@ int fhh_gb_garble(fhh_ctx* ctx, const uint8_t** gc_msg_dev, uint64_t* gc_msg_byt
     if (!gc_msg_dev || !gc_msg_bytes) return ctx->fail(FHH_E_ARG, "gb_garble: NULL argument");
     int rc = ctx_set_device(ctx);
     if (rc) return rc;
-    PartyState* Pp = ctx->party;
-    if (!Pp || Pp->role != 0 || Pp->step != 1) return ctx->fail(FHH_E_STATE, "gb_garble: call after fhh_gb_ot_labels");
-    PartyState& P = *Pp;
+    if (!ctx->party || ctx->party->in[0].step != 1) return ctx->fail(FHH_E_STATE, "gb_garble: call after fhh_gb_ot_labels");
+    PartyState& S = *ctx->party;
+    PartyInst& P = S.in[0];
     if (P.tests)
         HIP_TRY(ctx, P.plan.table ? launch_gt_garble(P.g, ctx->stream, ctx->protocol_grid)
                                   : launch_gc_garble(P.g, ctx->stream, ctx->protocol_grid));
-    rc = party_partials_to_host(ctx, P);
+    rc = party_partials_to_host(ctx, S);
     if (rc) return rc;
     rc = ctx_sync(ctx);
     if (rc) return rc;
@@ -716,9 +899,9 @@ int fhh_ev_evaluate(fhh_ctx* ctx, const uint8_t* gc_msg_dev, uint64_t gc_len, co
     if (!u_dev || !u_len) return ctx->fail(FHH_E_ARG, "ev_evaluate: NULL output");
     int rc = ctx_set_device(ctx);
     if (rc) return rc;
-    PartyState* Pp = ctx->party;
-    if (!Pp || Pp->role != 1 || Pp->step != 1) return ctx->fail(FHH_E_STATE, "ev_evaluate: call after fhh_ev_ot_labels");
-    PartyState& P = *Pp;
+    if (!ctx->party || ctx->party->in[1].step != 1) return ctx->fail(FHH_E_STATE, "ev_evaluate: call after fhh_ev_ot_labels");
+    PartyState& S = *ctx->party;
+    PartyInst& P = S.in[1];
     rc = check_in(ctx, gc_msg_dev, gc_len, gc_bytes(P), "gc message");
     if (rc) return rc;
     rc = check_in(ctx, y_dev, y_len, 0, "y (labels OT: empty since r05b)");
@@ -735,7 +918,7 @@ int fhh_ev_evaluate(fhh_ctx* ctx, const uint8_t* gc_msg_dev, uint64_t gc_len, co
     g.N = (uint32_t)P.n;
     g.nw = (uint32_t)P.plan.nw_gc;
     g.bits = P.bits;
-    g.gate_base = party_gate_base(P);
+    g.gate_base = party_gate_base(S, P);
     gc_layout(P, const_cast<uint8_t*>(gc_msg_dev), g);
     g.ev_labels = P.plan.tile_major ? P.T.as<uint4>() : P.labels.as<uint4>();   // r06: the tile-major T itself
     g.lab_tm = P.plan.tile_major ? 1u : 0u;
@@ -743,11 +926,11 @@ int fhh_ev_evaluate(fhh_ctx* ctx, const uint8_t* gc_msg_dev, uint64_t gc_len, co
     g.ev_ot = 1;
     g.out = P.out.as<uint8_t>();
     if (P.plan.fused_sums) {   // r06: added per child into the partials
-        g.node_partials = P.partials.as<uint64_t>();
+        g.node_partials = S.partials.as<uint64_t>();
         g.node_off = P.c_off;
     } else if (P.plan.lshare) {
         // r05c: its node value from its output label and the gc message's y, straight into the rows
-        g.sh_ev = reinterpret_cast<uint64_t*>(party_vals(P));
+        g.sh_ev = reinterpret_cast<uint64_t*>(party_vals(S, P));
     } else {
         g.out_packed = P.choices2.as<uint32_t>();
         g.out_dup = P.plan.per2;
@@ -755,7 +938,7 @@ int fhh_ev_evaluate(fhh_ctx* ctx, const uint8_t* gc_msg_dev, uint64_t gc_len, co
     if (P.tests)
         HIP_TRY(ctx, P.plan.table ? launch_gt_eval(g, ctx->stream, ctx->protocol_grid)
                                   : launch_gc_eval(g, ctx->stream, ctx->protocol_grid));
-    rc = party_partials_to_host(ctx, P);
+    rc = party_partials_to_host(ctx, S);
     if (rc) return rc;
     // 3. OT 2's receiver: choice = the GC output (collect.rs:461-471); T and U reused
     rc = party_ot_buffers(ctx, P, P.m2, true);
@@ -780,9 +963,9 @@ int fhh_gb_ot_shares(fhh_ctx* ctx, const uint8_t* u_dev, uint64_t u_len, const u
     if (!y_dev || !y_len) return ctx->fail(FHH_E_ARG, "gb_ot_shares: NULL output");
     int rc = ctx_set_device(ctx);
     if (rc) return rc;
-    PartyState* Pp = ctx->party;
-    if (!Pp || Pp->role != 0 || Pp->step != 2) return ctx->fail(FHH_E_STATE, "gb_ot_shares: call after fhh_gb_garble");
-    PartyState& P = *Pp;
+    if (!ctx->party || ctx->party->in[0].step != 2) return ctx->fail(FHH_E_STATE, "gb_ot_shares: call after fhh_gb_garble");
+    PartyState& S = *ctx->party;
+    PartyInst& P = S.in[0];
     rc = check_in(ctx, u_dev, u_len, P.m2 ? u_bytes(P.m2, P.ss_k) : 0, "U (shares OT)");
     if (rc) return rc;
     rc = party_ot_buffers(ctx, P, P.m2, false);
@@ -796,17 +979,16 @@ int fhh_gb_ot_shares(fhh_ctx* ctx, const uint8_t* u_dev, uint64_t u_len, const u
         a.mask = P.mask;
         a.U = const_cast<uint4*>(reinterpret_cast<const uint4*>(u_dev));
         for (int c = 0; c < 4; c++) a.s[c] = P.s[1][c];
-        a.sx = party_vals(P);
+        a.sx = party_vals(S, P);
         a.Y0 = P.Y.as<uint4>();
         HIP_TRY(ctx, party_ggm(P, a, false, ctx->stream));
         HIP_TRY(ctx, launch_ot_send_expand(a, ctx->stream, ctx->protocol_grid));
         HIP_TRY(ctx, launch_ot_send_hash_rows(a, ctx->stream, ctx->protocol_grid));
         if (P.last) HIP_TRY(ctx, launch_cot_fe255_finish(a, ctx->stream, ctx->protocol_grid));
     }
-    P.covered = P.c_off + P.C;
     rc = ctx_sync(ctx);
     if (rc) return rc;
-    P.step = 3;
+    party_finished(S, P);
     *y_dev = P.Y.as<uint8_t>();
     *y_len = y2_bytes(P);
     P.bytes_sent += *y_len;
@@ -817,9 +999,9 @@ int fhh_ev_ot_shares(fhh_ctx* ctx, const uint8_t* y_dev, uint64_t y_len) {
     CTX_CHECK(ctx);
     int rc = ctx_set_device(ctx);
     if (rc) return rc;
-    PartyState* Pp = ctx->party;
-    if (!Pp || Pp->role != 1 || Pp->step != 2) return ctx->fail(FHH_E_STATE, "ev_ot_shares: call after fhh_ev_evaluate");
-    PartyState& P = *Pp;
+    if (!ctx->party || ctx->party->in[1].step != 2) return ctx->fail(FHH_E_STATE, "ev_ot_shares: call after fhh_ev_evaluate");
+    PartyState& S = *ctx->party;
+    PartyInst& P = S.in[1];
     rc = check_in(ctx, y_dev, y_len, y2_bytes(P), "y (shares OT)");
     if (rc) return rc;
     if (P.m2) {   // the OT outputs are this server's node values, straight into the level's rows
@@ -827,26 +1009,26 @@ int fhh_ev_ot_shares(fhh_ctx* ctx, const uint8_t* y_dev, uint64_t y_len) {
         a.mode = P.last ? 3 : 2;
         a.choices = P.choices2.as<uint32_t>();
         a.Y0 = const_cast<uint4*>(reinterpret_cast<const uint4*>(y_dev));
-        a.out = reinterpret_cast<uint4*>(party_vals(P));
+        a.out = reinterpret_cast<uint4*>(party_vals(S, P));
         HIP_TRY(ctx, launch_ot_recv_hash_rows(a, ctx->stream, ctx->protocol_grid));
     }
-    P.covered = P.c_off + P.C;
     rc = ctx_sync(ctx);
     if (rc) return rc;
-    P.step = 3;
+    party_finished(S, P);
     return FHH_OK;
 }
 
 int fhh_party_node_sums(fhh_ctx* ctx, void* sums_a, void* sums_b) {
     CTX_CHECK(ctx);
+    std::vector<uint8_t> neg;
     if (ctx->group) {
         // every shard ran its own channel (fhh_shard_ctx); sum the shards' device values
         int S = 0;
         int rc = fhh_shard_info(ctx, 0, &S, nullptr, nullptr, nullptr, nullptr);
         if (rc) return rc;
         std::vector<const void*> v((size_t)S, nullptr);
-        std::vector<PartyState*> fused_shards;
-        std::vector<fhh_ctx*> ring_ctxs;
+        std::vector<PartyState*> states;
+        std::vector<fhh_ctx*> shard_ctxs;
         int last = -1, fused = -1, ring = -1;
         for (int k = 0; k < S; k++) {
             fhh_ctx* sh = nullptr;
@@ -856,11 +1038,11 @@ int fhh_party_node_sums(fhh_ctx* ctx, void* sums_a, void* sums_b) {
             if (rc) return rc;
             if (!nk) continue;
             PartyState* P = sh->party;
-            if (!P || P->step != 3 || P->covered != P->level_C)
+            if (!P || !party_level_done(*P))
                 return ctx->fail(FHH_E_STATE, "party_node_sums: shard " + std::to_string(k) +
                                                   "'s OTs are not finished for every child of the level");
-            if (last >= 0 && last != (int)P->last) return ctx->fail(FHH_E_STATE, "party_node_sums: shards disagree");
-            last = P->last;
+            if (last >= 0 && last != (int)P->level_last) return ctx->fail(FHH_E_STATE, "party_node_sums: shards disagree");
+            last = P->level_last;
             // one path for all: the fused host partials, or the stored values (a shard of the other kind has
             // nothing valid in the buffer that path reads)
             if (fused >= 0 && fused != (int)P->plan.fused_sums) return ctx->fail(FHH_E_STATE, "party_node_sums: shards disagree");
@@ -868,76 +1050,105 @@ int fhh_party_node_sums(fhh_ctx* ctx, void* sums_a, void* sums_b) {
             // FE or Z_2^32 shares (forms 0 and 2 are both fused at d = 1: the sums' group must agree too)
             if (ring >= 0 && ring != (int)P->plan.ring32) return ctx->fail(FHH_E_STATE, "party_node_sums: shards disagree");
             ring = P->plan.ring32;
+            // the sign is applied to the summed totals: the shards must be the same server and have run every child
+            // in the same role
+            if (!states.empty() && (sh->party_server != shard_ctxs[0]->party_server || P->level_C != states[0]->level_C ||
+                                    P->child_role != states[0]->child_role))
+                return ctx->fail(FHH_E_STATE, "party_node_sums: shards disagree");
             v[(size_t)k] = P->vals.p;
-            fused_shards.push_back(P);
-            ring_ctxs.push_back(sh);
+            states.push_back(P);
+            shard_ctxs.push_back(sh);
         }
         if (last < 0) return ctx->fail(FHH_E_STATE, "party_node_sums: no shard holds clients");
+        const uint64_t LC = states[0]->level_C;
+        rc = party_sign_flags(ctx, *states[0], shard_ctxs[0]->party_server, neg);
+        if (rc) return rc;
+        uint64_t* sums = static_cast<uint64_t*>(sums_a);
         if (ring == 1) {   // form 2: the shards' totals added, then reduced mod 2^32 once
-            const uint64_t LC = fused_shards[0]->level_C;
             std::vector<uint64_t> acc(LC, 0);
-            for (size_t j = 0; j < fused_shards.size(); j++) {
-                if (fused_shards[j]->level_C != LC) return ctx->fail(FHH_E_STATE, "party_node_sums: shards disagree");
-                rc = party_ring_totals(ring_ctxs[j], *fused_shards[j], acc);
+            for (size_t j = 0; j < states.size(); j++) {
+                rc = party_ring_totals(shard_ctxs[j], *states[j], acc);
                 if (rc) return ctx->fail(rc, std::string("party_node_sums: ") + g_err);
             }
-            uint64_t* sums = static_cast<uint64_t*>(sums_a);
             if (sums)
-                for (uint64_t c = 0; c < LC; c++) sums[c] = acc[c] & 0xFFFFFFFFull;
+                for (uint64_t c = 0; c < LC; c++) {
+                    sums[c] = acc[c] & 0xFFFFFFFFull;
+                    if (neg[c]) sums[c] = ring32_negate(sums[c]);
+                }
             return FHH_OK;
         }
         if (fused == 1) {   // r06: the shards' host partials, summed
-            const uint64_t LC = fused_shards[0]->level_C;
             std::vector<uint64_t> h(LC * 2, 0);
-            for (PartyState* P : fused_shards) {
-                if (!P->plan.fused_sums || P->level_C != LC) return ctx->fail(FHH_E_STATE, "party_node_sums: shards disagree");
-                const int k0 = P->role == 0 ? 0 : 2;
+            for (PartyState* P : states)
                 for (uint64_t c = 0; c < LC; c++) {
-                    h[2 * c] += P->partials_host[4 * c + k0];
-                    h[2 * c + 1] += P->partials_host[4 * c + k0 + 1];
+                    h[2 * c] += P->partials_host[4 * c] + P->partials_host[4 * c + 2];
+                    h[2 * c + 1] += P->partials_host[4 * c + 1] + P->partials_host[4 * c + 3];
                 }
-            }
-            uint64_t* sums = static_cast<uint64_t*>(sums_a);
             if (sums)
-                for (uint64_t c = 0; c < LC; c++) sums[c] = fhh::fe_canon_from_limbs(h[2 * c], h[2 * c + 1]);
+                for (uint64_t c = 0; c < LC; c++) {
+                    sums[c] = fhh::fe_canon_from_limbs(h[2 * c], h[2 * c + 1]);
+                    if (neg[c]) sums[c] = fe_negate(sums[c]);
+                }
             return FHH_OK;
         }
         const uint32_t fmt = last ? FHH_VALS_FE255_BLOCKPAIR : FHH_VALS_FE_U64;
-        return group_node_sums(ctx, v.data(), false, 0, fmt, sums_a, sums_b);   // ld 0: each shard's n
-    }
-    PartyState* Pp = ctx->party;
-    if (!Pp || Pp->step != 3 || Pp->covered != Pp->level_C)
-        return ctx->fail(FHH_E_STATE, "party_node_sums: the level's OTs are not finished for every child");
-    PartyState& P = *Pp;
-    if (P.plan.ring32) {   // form 2: the party's sum mod 2^32, zero-extended
-        std::vector<uint64_t> acc(P.level_C, 0);
-        int rc = party_ring_totals(ctx, P, acc);
+        rc = group_node_sums(ctx, v.data(), false, 0, fmt, sums_a, sums_b);   // ld 0: each shard's n
         if (rc) return rc;
-        uint64_t* sums = static_cast<uint64_t*>(sums_a);
-        if (sums)
-            for (uint64_t c = 0; c < P.level_C; c++) sums[c] = acc[c] & 0xFFFFFFFFull;
+        if (last) {
+            party_negate_last(shard_ctxs, neg, static_cast<uint32_t*>(sums_a), static_cast<uint32_t*>(sums_b));
+        } else if (sums) {
+            for (uint64_t c = 0; c < LC; c++)
+                if (neg[c]) sums[c] = fe_negate(sums[c]);
+        }
         return FHH_OK;
     }
-    if (P.plan.fused_sums) {   // r06: the partials the garble / evaluate calls copied to the host
-        const int k0 = P.role == 0 ? 0 : 2;
-        uint64_t* sums = static_cast<uint64_t*>(sums_a);
+    if (!ctx->party || !party_level_done(*ctx->party))
+        return ctx->fail(FHH_E_STATE, "party_node_sums: the level's OTs are not finished for every child");
+    PartyState& S = *ctx->party;
+    int rc = party_sign_flags(ctx, S, ctx->party_server, neg);
+    if (rc) return rc;
+    uint64_t* sums = static_cast<uint64_t*>(sums_a);
+    if (S.plan.ring32) {   // form 2: the party's sum mod 2^32, zero-extended
+        std::vector<uint64_t> acc(S.level_C, 0);
+        rc = party_ring_totals(ctx, S, acc);
+        if (rc) return rc;
         if (sums)
-            for (uint64_t c = 0; c < P.level_C; c++)
-                sums[c] = fhh::fe_canon_from_limbs(P.partials_host[4 * c + k0], P.partials_host[4 * c + k0 + 1]);
+            for (uint64_t c = 0; c < S.level_C; c++) {
+                sums[c] = acc[c] & 0xFFFFFFFFull;
+                if (neg[c]) sums[c] = ring32_negate(sums[c]);
+            }
+        return FHH_OK;
+    }
+    if (S.plan.fused_sums) {   // r06: the partials the garble / evaluate calls copied to the host
+        const std::vector<uint64_t>& h = S.partials_host;
+        if (sums)
+            for (uint64_t c = 0; c < S.level_C; c++) {
+                sums[c] = fhh::fe_canon_from_limbs(h[4 * c] + h[4 * c + 2], h[4 * c + 1] + h[4 * c + 3]);
+                if (neg[c]) sums[c] = fe_negate(sums[c]);
+            }
         return FHH_OK;
     }
     // the garbler's value is r1 = v + mask, the evaluator's its C-OT output (written per chunk into
-    // P.vals); rows of n values: FE as u64, FieldElm as a BlockPair (2 blocks)
-    const void* vv[1] = {P.vals.p};
-    if (P.last)
-        return fhh_node_sums_fe255_device(ctx, vv, P.n, FHH_VALS_FE255_BLOCKPAIR, static_cast<uint32_t*>(sums_a),
-                                          static_cast<uint32_t*>(sums_b));
-    return fhh_node_sums_fe_device(ctx, vv, P.n, FHH_VALS_FE_U64, static_cast<uint64_t*>(sums_a));
+    // the level's vals); rows of n values: FE as u64, FieldElm as a BlockPair (2 blocks)
+    const void* vv[1] = {S.vals.p};
+    if (S.level_last) {
+        rc = fhh_node_sums_fe255_device(ctx, vv, S.n, FHH_VALS_FE255_BLOCKPAIR, static_cast<uint32_t*>(sums_a),
+                                        static_cast<uint32_t*>(sums_b));
+        if (rc) return rc;
+        party_negate_last({ctx}, neg, static_cast<uint32_t*>(sums_a), static_cast<uint32_t*>(sums_b));
+        return FHH_OK;
+    }
+    rc = fhh_node_sums_fe_device(ctx, vv, S.n, FHH_VALS_FE_U64, sums);
+    if (rc) return rc;
+    if (sums)
+        for (uint64_t c = 0; c < S.level_C; c++)
+            if (neg[c]) sums[c] = fe_negate(sums[c]);
+    return FHH_OK;
 }
 
 int fhh_party_bytes_sent(const fhh_ctx* ctx, uint64_t* bytes) {
     CTX_CHECK(ctx);
-    if (bytes) *bytes = ctx->party ? ctx->party->bytes_sent : 0;
+    if (bytes) *bytes = ctx->party ? ctx->party->in[0].bytes_sent + ctx->party->in[1].bytes_sent : 0;
     return FHH_OK;
 }
 

@@ -731,6 +731,7 @@ int fhh_reset(fhh_ctx* ctx) {
     ctx->last_hist.clear();
     ctx->pending_C = 0;
     ctx->level = 0;
+    ctx->party_server = -1;
     for (auto& T : ctx->tab) {
         T.live.clear();
         // entries are sized by npad: the next collection may be larger, so its tables are sized afresh (the

@@ -180,31 +180,83 @@ def _out():
     return ctypes.c_void_p(), ctypes.c_uint64()
 
 
+class _Chunk:
+    """One chunk between a garbling and an evaluating collection, call by call (the stages a split level
+    interleaves). `busy` ([server 0, server 1] seconds, or None) receives the wall time of every party call,
+    charged to the server whose ctx ran it (each call returns after its device work is complete)."""
+
+    def __init__(self, gb: KeyCollection, ev: KeyCollection, cfg_gb: FhhGbCfg, cfg_ev: FhhEvCfg, to_gb: Channel,
+                 to_ev: Channel, busy=None, garbler: int = 0):
+        self.gb, self.ev, self.cfg_gb, self.cfg_ev, self.to_gb, self.to_ev = gb, ev, cfg_gb, cfg_ev, to_gb, to_ev
+        self.busy, self.garbler = busy, garbler
+        self.sizes = {}
+
+    def _call(self, evaluator: bool, kc: KeyCollection, fn, *args):
+        t = time.perf_counter()
+        rc = fn(kc.handle, *args)
+        if self.busy is not None:
+            self.busy[self.garbler ^ int(evaluator)] += time.perf_counter() - t
+        check(rc, kc.handle)
+
+    def ev_labels(self):
+        L = lib()
+        u1, u1n = _out()
+        self._call(True, self.ev, L.fhh_ev_ot_labels, ctypes.byref(self.cfg_ev), ctypes.byref(u1), ctypes.byref(u1n))
+        self.u1_rx = self.to_gb.send("u", u1.value or 0, u1n.value)
+        self.sizes["u1"] = u1n.value
+
+    def gb_labels(self):
+        self.y1, self.y1n = _out()
+        self._call(False, self.gb, lib().fhh_gb_ot_labels, ctypes.byref(self.cfg_gb), ctypes.c_void_p(self.u1_rx),
+                   self.sizes["u1"], ctypes.byref(self.y1), ctypes.byref(self.y1n))
+        self.sizes["y1"] = self.y1n.value
+
+    def garble(self):
+        gc, gcn = _out()
+        self._call(False, self.gb, lib().fhh_gb_garble, ctypes.byref(gc), ctypes.byref(gcn))
+        self.y1_rx = self.to_ev.send("y1", self.y1.value or 0, self.y1n.value)
+        self.gc_rx = self.to_ev.send("gc", gc.value or 0, gcn.value)
+        self.sizes["gc"] = gcn.value
+
+    def evaluate(self):
+        u2, u2n = _out()
+        self._call(True, self.ev, lib().fhh_ev_evaluate, ctypes.c_void_p(self.gc_rx), self.sizes["gc"],
+                   ctypes.c_void_p(self.y1_rx), self.sizes["y1"], ctypes.byref(u2), ctypes.byref(u2n))
+        self.u2_rx = self.to_gb.send("u", u2.value or 0, u2n.value)
+        self.sizes["u2"] = u2n.value
+
+    def shares(self):
+        y2, y2n = _out()
+        self._call(False, self.gb, lib().fhh_gb_ot_shares, ctypes.c_void_p(self.u2_rx), self.sizes["u2"],
+                   ctypes.byref(y2), ctypes.byref(y2n))
+        y2_rx = self.to_ev.send("y2", y2.value or 0, y2n.value)
+        self._call(True, self.ev, lib().fhh_ev_ot_shares, ctypes.c_void_p(y2_rx), y2n.value)
+        self.sizes["y2"] = y2n.value
+
+    def run(self) -> dict:
+        for stage in (self.ev_labels, self.gb_labels, self.garble, self.evaluate, self.shares):
+            stage()
+        return {name: self.sizes[name] for name in ("u1", "y1", "gc", "u2", "y2")}
+
+
 def run_chunk(gb: KeyCollection, ev: KeyCollection, cfg_gb: FhhGbCfg, cfg_ev: FhhEvCfg, to_gb: Channel,
-              to_ev: Channel) -> dict:
+              to_ev: Channel, busy=None, garbler: int = 0) -> dict:
     """One chunk's GC + OT, each call on its own server's ctx with its own cfg; returns the message
     sizes (u1, y1, gc, u2, y2)."""
-    L = lib()
-    u1, u1n = _out()
-    check(L.fhh_ev_ot_labels(ev.handle, ctypes.byref(cfg_ev), ctypes.byref(u1), ctypes.byref(u1n)), ev.handle)
-    u1_rx = to_gb.send("u", u1.value or 0, u1n.value)
-    y1, y1n = _out()
-    check(L.fhh_gb_ot_labels(gb.handle, ctypes.byref(cfg_gb), ctypes.c_void_p(u1_rx), u1n.value, ctypes.byref(y1),
-                             ctypes.byref(y1n)), gb.handle)
-    gc, gcn = _out()
-    check(L.fhh_gb_garble(gb.handle, ctypes.byref(gc), ctypes.byref(gcn)), gb.handle)
-    y1_rx = to_ev.send("y1", y1.value or 0, y1n.value)
-    gc_rx = to_ev.send("gc", gc.value or 0, gcn.value)
-    u2, u2n = _out()
-    check(L.fhh_ev_evaluate(ev.handle, ctypes.c_void_p(gc_rx), gcn.value, ctypes.c_void_p(y1_rx), y1n.value,
-                            ctypes.byref(u2), ctypes.byref(u2n)), ev.handle)
-    u2_rx = to_gb.send("u", u2.value or 0, u2n.value)
-    y2, y2n = _out()
-    check(L.fhh_gb_ot_shares(gb.handle, ctypes.c_void_p(u2_rx), u2n.value, ctypes.byref(y2), ctypes.byref(y2n)),
-          gb.handle)
-    y2_rx = to_ev.send("y2", y2.value or 0, y2n.value)
-    check(L.fhh_ev_ot_shares(ev.handle, ctypes.c_void_p(y2_rx), y2n.value), ev.handle)
-    return {"u1": u1n.value, "y1": y1n.value, "gc": gcn.value, "u2": u2n.value, "y2": y2n.value}
+    return _Chunk(gb, ev, cfg_gb, cfg_ev, to_gb, to_ev, busy, garbler).run()
+
+
+def run_chunk_pair(first: _Chunk, second: _Chunk) -> list:
+    """Two windows of a split level, garbled by different servers (include/fhh.h, the split level's call order):
+    both labels OTs, then both servers garble (at once on two machines), both evaluate, and at the FieldElm
+    level the share OTs in both directions. Returns both windows' message sizes."""
+    for ch in (first, second):
+        ch.ev_labels()
+        ch.gb_labels()
+    for stage in ("garble", "evaluate", "shares"):
+        for ch in (first, second):
+            getattr(ch, stage)()
+    return [{name: ch.sizes[name] for name in ("u1", "y1", "gc", "u2", "y2")} for ch in (first, second)]
 
 
 def party_sums(kc: KeyCollection, C: int, last: bool):
@@ -228,11 +280,15 @@ class TwoPartyResult:
     base_ot_runs: int = 0                                # Chou–Orlandi runs (128 OTs each)
     base_ot_bytes: int = 0                               # their messages (A, B) over the channel
     base_ot_wait_s: float = 0.0                          # crawl time spent waiting for base OTs
+    direction_bytes: list = field(default_factory=lambda: [0, 0])   # chunk message bytes [to server 0, to server 1]
 
 
 # bytes per test of both parties' chunk buffers at d = 1 (gc message 81, labels 32 + 32, OT matrices
 # and messages ~150, node values 16, with headroom): the auto chunk size's divisor
 _PARTY_BYTES_PER_TEST = 512
+
+# who garbles a window (fhh_party_role_plan's modes)
+ROLE_MODES = {"fixed": 0, "swapped": 1, "level": 2, "split": 3}
 
 
 def chunk_windows(C: int, chunk_children: int):
@@ -248,7 +304,8 @@ def two_party_crawl(c0: KeyCollection, c1: KeyCollection, threshold: float, ncli
                     chunk_children: int | None = None, chunk_bytes: int = 64 << 30,
                     level_log: list | None = None, base_ot_every: str = "level",
                     base_ot_workers: int | None = None, base_ot_ahead: int = 8,
-                    form: str = "table", ot_ss_k: int = 1, start_paths=None) -> TwoPartyResult:
+                    form: str = "table", ot_ss_k: int = 1, start_paths=None, roles: str = "fixed",
+                    server_busy: list | None = None) -> TwoPartyResult:
     """The leader's level loop (leader.rs:417-440) with the GC + OT of every level split between the
     two servers' ctxs (server 0 garbles / sends, server 1 evaluates / receives): crawl both, run the
     level's protocol through the channel, take each server's node sums from its own device
@@ -283,7 +340,21 @@ def two_party_crawl(c0: KeyCollection, c1: KeyCollection, threshold: float, ncli
     `start_paths` (None: the root): a frontier [F][d][depth], as `KeyCollection.tree_init_at` takes it — a
     checkpoint's `frontier_paths`, or one part of a split prefix space. Both collections start there instead
     of `tree_init` and the loop runs levels depth .. L - 1; the base OTs, `expect_counts` and `level_log` stay
-    indexed by the real level, and the per-level lists of the result hold those levels only."""
+    indexed by the real level, and the per-level lists of the result hold those levels only.
+
+    `roles` (public, like form): who garbles. "fixed" (the default): server 0, as the reference. "swapped":
+    server 1. "level": server `level & 1`. "split": a level's windows alternate between the servers, starting
+    with `level & 1` (fhh_party_role_plan; a level that would be one window is cut in two), so that on two
+    machines both GPUs garble and evaluate at once: each pair of windows runs as `run_chunk_pair`. Each pair of
+    shards has a GarblerParty and an EvaluatorParty on BOTH collections, base OTs run in the direction(s) a
+    level uses (with "split": both), each server draws its own Delta, masks and CO15 seeds, and both
+    collections are told which server they are (`party_set_server`), so the node sums come out with the
+    reference's sign and the leader's keep_values / final_values are unchanged. material "test" derives the
+    second direction's material from prf_seed with a direction bit. `server_busy` (a list [server 0, server 1])
+    accumulates the wall seconds of each server's own fhh_gb_* / fhh_ev_* calls."""
+    if roles not in ROLE_MODES:
+        raise ValueError(f"two_party_crawl: roles {roles!r}")
+    role_mode = ROLE_MODES[roles]
     if ot_ss_k not in (1, 2, 4):
         raise ValueError(f"two_party_crawl: ot_ss_k {ot_ss_k!r}")
     if material not in ("fresh", "test"):
@@ -311,8 +382,12 @@ def two_party_crawl(c0: KeyCollection, c1: KeyCollection, threshold: float, ncli
     shards = [(c0.shard(k), c1.shard(k)) for k in range(S)] if S > 1 else [(c0, c1)]
     if channel == "inplace" and any(a.device != b.device for a, b in shards):
         raise ValueError("two_party_crawl: an in-place channel needs both parties of a pair on one GPU")
-    chans = [(Channel(a.device, channel), Channel(b.device, channel)) for a, b in shards]
-    parties = [(GarblerParty(a), EvaluatorParty(b)) for a, b in shards]
+    # per pair of shards and direction g (the garbling server): (to the garbler, to the evaluator), and the two
+    # parties; direction 1 has server 1's collection garbling
+    sides = [((a, b), (b, a)) for a, b in shards]
+    chans = [tuple((Channel(gb.device, channel), Channel(ev.device, channel)) for gb, ev in sd) for sd in sides]
+    parties = [tuple((GarblerParty(gb), EvaluatorParty(ev)) for gb, ev in sd) for sd in sides]
+    level_dirs = {0: lambda lv: (0,), 1: lambda lv: (1,), 2: lambda lv: (lv & 1,), 3: lambda lv: (0, 1)}[role_mode]
     res = TwoPartyResult()
     shard_clients = [a.num_clients() for a, _ in shards]
     # base OTs: a pool computing each (level, shard)'s CO15 runs (labels; + the share OT's at the last level) ahead
@@ -322,9 +397,9 @@ def two_party_crawl(c0: KeyCollection, c1: KeyCollection, threshold: float, ncli
         nworkers = base_ot_workers or min(16, os.cpu_count() or 4)
         pool = ThreadPoolExecutor(max_workers=nworkers)
 
-        def runs(k, kinds):
-            gbp, evp = parties[k]
-            to_gb, to_ev = chans[k]
+        def runs(k, g, kinds):
+            gbp, evp = parties[k][g]
+            to_gb, to_ev = chans[k][g]
             # kind 0 labels (s = Delta: colour bit), kind 1 the share OT — at the FieldElm level only (r05c)
             return [base_ot_run(gbp, evp, to_gb, to_ev, colour=(w == 0)) for w in range(kinds)]
 
@@ -332,28 +407,33 @@ def two_party_crawl(c0: KeyCollection, c1: KeyCollection, threshold: float, ncli
             key = 0 if base_ot_every == "crawl" else lv
             kinds = 2 if (base_ot_every == "crawl" or lv == L - 1) else 1
             for k in range(len(shards)):
-                if shard_clients[k] and (key, k) not in pending:
-                    pending[(key, k)] = pool.submit(runs, k, kinds)
+                for g in (level_dirs(lv) if base_ot_every == "level" else sorted({g for v in range(lv0, L) for g in level_dirs(v)})):
+                    if shard_clients[k] and (key, k, g) not in pending:
+                        pending[(key, k, g)] = pool.submit(runs, k, g, kinds)
 
         for lv in range(lv0, min(L, lv0 + base_ot_ahead)):
             submit(lv)
 
-    def level_base(lv, k):
+    def level_base(lv, k, g):
         key = 0 if base_ot_every == "crawl" else lv
         t = time.perf_counter()
-        got = pending[(key, k)].result()
+        got = pending[(key, k, g)].result()
         res.base_ot_wait_s += time.perf_counter() - t
         if base_ot_every == "level":
-            del pending[(key, k)]
-        return [g for g, _ in got], [e for _, e in got]
+            del pending[(key, k, g)]
+        return [gb for gb, _ in got], [e for _, e in got]
 
     from .fields import FE255_P, FE_P
     tm = timing if timing is not None else {}
     for k in ("crawl", "gcot", "node_sums", "keep", "prune"):
         tm.setdefault(k, 0.0)
+    busy = server_busy
     clock = time.perf_counter
     if chunk_children is None:
         chunk_children = max(1, chunk_bytes // (_PARTY_BYTES_PER_TEST * max(1, max(shard_clients))))
+        # a split level on one GPU: each ctx holds both instances' buffers
+        if role_mode == 3 and any(a.device == b.device for a, b in shards):
+            chunk_children = max(1, chunk_children // 2)
     try:
         if start_paths is not None:   # (inside the try: refused paths must not leave the base-OT pool running)
             c0.tree_init_at(start_paths)
@@ -361,6 +441,8 @@ def two_party_crawl(c0: KeyCollection, c1: KeyCollection, threshold: float, ncli
         else:
             c0.tree_init()
             c1.tree_init()
+        c0.party_set_server(0)
+        c1.party_set_server(1)
         for lv in range(lv0, L):
             last = lv == L - 1
             if pool is not None and lv + base_ot_ahead < L:
@@ -371,24 +453,39 @@ def two_party_crawl(c0: KeyCollection, c1: KeyCollection, threshold: float, ncli
             assert C0 == C1
             t1 = clock()
             sizes = {}
-            for k, ((a, b), (to_gb, to_ev)) in enumerate(zip(shards, chans)):
+            # the level's windows and who garbles each; a whole-level window keeps child_count = 0
+            plan = [(cb, 0 if cc == C0 else cc, g)
+                    for cb, cc, g in KeyCollection.party_role_plan(C0, chunk_children, lv, role_mode)]
+            for k in range(len(shards)):
                 if shard_clients[k] == 0:
                     continue
-                gbp, evp = parties[k]
                 if material == "fresh":
-                    gb_base, ev_base = level_base(lv, k)
-                for j, (cb, cc) in enumerate(chunk_windows(C0, chunk_children)):
+                    base = {g: level_base(lv, k, g) for g in level_dirs(lv)}
+                chunks = []
+                for j, (cb, cc, g) in enumerate(plan):
+                    gbp, evp = parties[k][g]
                     if material == "fresh":
-                        cfg_gb = gbp.chunk_cfg(gb_base, cb, cc, form_id)
-                        cfg_ev = evp.chunk_cfg(ev_base, cb, cc, form_id)
+                        cfg_gb = gbp.chunk_cfg(base[g][0], cb, cc, form_id)
+                        cfg_ev = evp.chunk_cfg(base[g][1], cb, cc, form_id)
                     else:
-                        cfg_gb, cfg_ev = test_cfgs(prf_seed ^ (k << 40) ^ (j << 48), lv)
+                        cfg_gb, cfg_ev = test_cfgs(prf_seed ^ (k << 40) ^ (j << 48) ^ (g << 39), lv)
                         cfg_gb.child_begin, cfg_gb.child_count = cb, cc
                         cfg_ev.child_begin, cfg_ev.child_count = cb, cc
                         cfg_gb.form = cfg_ev.form = form_id
                     cfg_gb.ot_ss_k = cfg_ev.ot_ss_k = ot_ss_k
-                    for name, v in run_chunk(a, b, cfg_gb, cfg_ev, to_gb, to_ev).items():
-                        sizes[name] = sizes.get(name, 0) + v
+                    chunks.append(_Chunk(gbp.kc, evp.kc, cfg_gb, cfg_ev, *chans[k][g], busy=busy, garbler=g))
+                # a split level runs its windows in pairs (the two garble at once on two machines); every other
+                # level, and a window left over, one by one
+                at = 0
+                while at < len(chunks):
+                    if at + 1 < len(chunks) and chunks[at].garbler != chunks[at + 1].garbler:
+                        done = run_chunk_pair(chunks[at], chunks[at + 1])
+                    else:
+                        done = [chunks[at].run()]
+                    at += len(done)
+                    for sz in done:
+                        for name, v in sz.items():
+                            sizes[name] = sizes.get(name, 0) + v
             res.level_bytes.append(sizes)
             t2 = clock()
             s0 = party_sums(c0, C0, last)
@@ -430,10 +527,15 @@ def two_party_crawl(c0: KeyCollection, c1: KeyCollection, threshold: float, ncli
                 f.cancel()
             pool.shutdown(wait=True)
     res.final = KeyCollection.final_values(c0.final_shares(), c1.final_shares())
-    res.base_ot_bytes = sum(a.host_bytes + b.host_bytes for a, b in chans)
+    res.base_ot_bytes = sum(a.host_bytes + b.host_bytes for ch in chans for a, b in ch)
+    # direction g's garbler is server g: its channel to the garbler ends at server g, the other at server 1 - g
+    for ch in chans:
+        for g, (to_gb, to_ev) in enumerate(ch):
+            res.direction_bytes[g] += to_gb.bytes
+            res.direction_bytes[1 - g] += to_ev.bytes
     res.base_ot_runs = res.base_ot_bytes // (65 + 128 * 65) if res.base_ot_bytes else 0
     return res
 
 
 __all__ = ["Channel", "GarblerParty", "EvaluatorParty", "base_ot_run", "test_cfgs", "run_chunk", "party_sums",
-           "two_party_crawl", "TwoPartyResult", "chunk_windows"]
+           "run_chunk_pair", "two_party_crawl", "TwoPartyResult", "chunk_windows", "ROLE_MODES"]

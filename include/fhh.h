@@ -878,7 +878,8 @@ int fhh_gt_cot_ring32_host(fhh_ctx* ctx, uint64_t n, uint32_t bits, const uint8_
  * child_count) only (C above = the chunk's children) — one protocol instance per chunk, as the
  * reference's channels each run a slice of the level's tests (collect.rs:423-430); this bounds the
  * level's buffers at 1M clients. Chunks run in order and together cover [0, C); fhh_party_node_sums
- * follows the last one. Both parties must use the same windows. child_count = 0: the whole level.
+ * follows the last one. Both parties must use the same windows. child_count = 0: the whole level. The role may
+ * change from chunk to chunk (a level split between the servers, below).
  * Freshness: Delta is the labels session's s (fresh with each base-OT run: run the base OTs per level,
  * as the reference's init per channel does); the mask should be fresh per chunk (gate tweaks are indexed
  * by the test's index in the whole level). Base OTs may be reused across chunks: each
@@ -920,8 +921,59 @@ int fhh_ev_ot_shares(fhh_ctx* ctx, const uint8_t* y_dev, uint64_t y_bytes);
 /* sums_a = uint64_t[C] (non-last level: canonical FE, or after a form-2 level the sum mod 2^32) or
  * uint32_t[C][10] unreduced (last); sums_b = NULL or uint32_t[C][8] canonical (last level) */
 int fhh_party_node_sums(fhh_ctx* ctx, void* sums_a, void* sums_b);
-/* bytes this ctx sent in the level so far (its outgoing messages) */
+/* bytes this ctx sent in the level so far (its outgoing messages, over both of its instances) */
 int fhh_party_bytes_sent(const fhh_ctx* ctx, uint64_t* bytes);
+
+/* ---- a level split between the servers: per-chunk roles ---------------------------------------
+ * Garbling costs more than evaluating, and a level cannot start before the previous one is pruned, so with
+ * one garbler the other server's machine idles for part of every level. A ctx therefore holds TWO protocol
+ * instances, the garbler's (every fhh_gb_* call) and the evaluator's (every fhh_ev_* call), each with its own
+ * chunk buffers, base-OT sessions and row-PRG counters, step counter and byte count; the level's storage
+ * (node values or fused partials, the form, C) is shared by both and set up by the level's first chunk,
+ * whichever role opens it. A level's chunks may then alternate roles — server 0 garbles windows 0, 2, 4, ...
+ * and evaluates 1, 3, 5, ..., server 1 the reverse — and the calls of the two instances interleave freely on the
+ * ctx's stream. Per pair of windows (w, w') the servers call, in this order:
+ *   server 0                                              server 1
+ *                                      <--------------  fhh_ev_ot_labels(w) -> u1
+ *   fhh_gb_ot_labels(w, u1)
+ *   fhh_ev_ot_labels(w') -> u1'        -------------->
+ *                                                        fhh_gb_ot_labels(w', u1')
+ *   fhh_gb_garble -> gc(w)             <------------->   fhh_gb_garble -> gc(w')      (both GPUs at once)
+ *   fhh_ev_evaluate(gc(w'))                              fhh_ev_evaluate(gc(w))
+ *   (FieldElm level) fhh_gb_ot_shares / fhh_ev_ot_shares in both directions
+ * Opening rule (both *_ot_labels calls): a chunk begins where the last chunk opened in this level ended, in
+ * EITHER role (child_begin = 0 starts a level), and the instance it reuses has finished its previous chunk;
+ * FHH_E_STATE otherwise. In one role throughout this is the rule of the chunks above. fhh_party_node_sums needs the
+ * finished chunks of both instances to cover [0, C) exactly. Each direction has its own base OTs: an instance's
+ * sessions and counters are per (ctx, role). This is a protocol form outside the reference, like SoftSpoken and
+ * form 2: the reference fixes gc_sender per server. Every chunk's messages are those of the same chunk run with
+ * the garbling server's planes as the garbler's bits.
+ *
+ * The sign. The shares of a test come out as garbler - evaluator = eq, and the leader computes v0 - v1. With
+ * fhh_party_set_server(ctx, 0 or 1), fhh_party_node_sums negates child c's sum iff this ctx is server 0 and
+ * EVALUATED c, or is server 1 and GARBLED c: v0 - v1 is then the count for every child whoever garbled it, and
+ * the leader (fhh_keep_values, fhh_keep_values_ring32, fhh_keep_values_last, fhh_final_values) stays the
+ * reference's. Negated: FE p - s (0 stays 0); form 2 (2^32 - s) mod 2^32 zero-extended; FieldElm level the
+ * canonical -s mod 2^255 - 19, which is then both the unreduced output (zero-extended to 10 limbs) and the
+ * recorded value fhh_final_shares hands out. The setting holds until fhh_reset or fhh_destroy; on a multi-device
+ * ctx it applies to every shard. FHH_E_ARG outside {-1, 0, 1}; FHH_E_STATE while a level's protocol is open.
+ * Unset (-1, the default): a level run wholly in one role is summed as ever (the sign is the caller's business);
+ * a level whose chunks mixed roles is refused by fhh_party_node_sums (FHH_E_STATE). */
+int fhh_party_set_server(fhh_ctx* ctx, int server);
+/* The windows of a level of n_children children and who garbles each — host only, computed alike by both
+ * servers. mode 0 fixed: the windows of chunk_children children (0, or a level that fits: one window), garbler 0
+ * for all; 1 swapped: the same windows, garbler 1; 2 by level: garbler = level & 1; 3 split: the same windows,
+ * except that a level of C >= 2 that would be one window is cut into ceil(C / 2) and floor(C / 2); the garblers
+ * alternate, starting with level & 1 (so a one-child level still alternates over the levels). Windows are
+ * ascending, contiguous and cover [0, C); count[] holds the real counts (a one-window level: C). n_windows is
+ * always written; begin / count / garbler are all NULL (the count alone) or arrays of cap >= n_windows entries.
+ * FHH_E_ARG: mode > 3, NULL n_windows, some but not all arrays NULL, cap too small. */
+int fhh_party_role_plan(uint64_t n_children, uint64_t chunk_children, uint32_t level, uint32_t mode, uint64_t cap,
+                        uint64_t* n_windows, uint64_t* begin, uint64_t* count, uint8_t* garbler);
+/* The negation fhh_party_node_sums applies, on one host value: fmt 0 FE (uint64_t in / out, canonical), 1 Z_2^32
+ * (uint64_t zero-extended), 2 FieldElm (in uint32_t[10] unreduced, out uint32_t[8] canonical). FHH_E_ARG: fmt > 2,
+ * a NULL buffer, an FE value >= p or a Z_2^32 value >= 2^32. */
+int fhh_party_negate(uint32_t fmt, const void* in, void* out);
 /* TEST MODE ONLY: both parties' configs derived from one seed — the in-process level loop's material
  * (fhh_sim_config.gc = 2, ideal base OTs) for prf_seed and level, so a two-ctx run can mirror
  * fhh_sim_crawl. Not private (one seed knows both sides); a deployment draws each party's
