@@ -57,11 +57,12 @@ EXPORTS = [
     "fhh_party_node_sums", "fhh_party_bytes_sent", "fhh_gc_party_test_cfgs", "fhh_memcpy_device",
     "fhh_cot_extend_host", "fhh_cot_extend_ss_host", "fhh_gc_cot_host", "fhh_gt_cot_host", "fhh_gt_cot_ring32_host",
     "fhh_shard_plan", "fhh_reserve_clients", "fhh_add_keys_bincode_append",
-    "fhh_bincode_request_bytes", "fhh_export_keys_bincode",
+    "fhh_bincode_request_bytes", "fhh_export_keys_bincode", "fhh_export_timing",
     "fhh_frontier_plan", "fhh_tree_init_at", "fhh_frontier_paths",
     "fhh_retain_clients", "fhh_retain_plan", "fhh_retain_timing",
     "fhh_retain_clients_device", "fhh_retain_plan_device", "fhh_retain_mask_timing",
     "fhh_gen_keys_ball", "fhh_ball_bounds",
+    "fhh_leader_requests_ball", "fhh_leader_requests_ball_device", "fhh_leader_requests_plan",
     "fhh_party_set_server", "fhh_party_role_plan", "fhh_party_negate",
 ]
 
@@ -119,7 +120,7 @@ class FhhSimConfig(ctypes.Structure):
     ]
 
 
-SOURCES = ("fhh_kernels.hip", "fhh_bincode_out.hip", "fhh_retain.hip", "fhh_retain_mask.hip", "fhh_sketch.hip", "fhh_gc.hip", "fhh_ot.hip",
+SOURCES = ("fhh_kernels.hip", "fhh_bincode_out.hip", "fhh_leader_requests.hip", "fhh_retain.hip", "fhh_retain_mask.hip", "fhh_sketch.hip", "fhh_gc.hip", "fhh_ot.hip",
            "fhh_loop.hip", "fhh_microbench.hip", "fhh_host.cpp", "fhh_keys_io.cpp", "fhh_retain.cpp", "fhh_ball.cpp",
            "fhh_sim_crawl.cpp", "fhh_sketch_host.cpp",
            "fhh_gcot.cpp", "fhh_gcot_harness.cpp", "fhh_group.cpp", "fhh_comm.cpp", "fhh_base_ot.cpp")
@@ -340,11 +341,15 @@ def lib():
         "fhh_gen_keys_pair": (i, [vp, vp, u64, u8p, u8p, u8p]),
         "fhh_gen_keys_ball": (i, [vp, vp, u64, P(FhhBallSrc)]),
         "fhh_ball_bounds": (i, [u32, u32, u64, P(FhhBallSrc), u8p, u8p, u8p, u64p]),
+        "fhh_leader_requests_plan": (i, [u32, u32, u64, u64p, u64p, u64p]),
+        "fhh_leader_requests_ball_device": (i, [vp, u64, P(FhhBallSrc), u64, P(vp), P(vp), u64p]),
+        "fhh_leader_requests_ball": (i, [vp, u64, P(FhhBallSrc), u64, u8p, u8p, u64, u64p]),
         "fhh_add_keys_bincode": (i, [vp, u8p, u64]),
         "fhh_reserve_clients": (i, [vp, u64]),
         "fhh_add_keys_bincode_append": (i, [vp, u8p, u64]),
         "fhh_bincode_request_bytes": (i, [u32, u32, u64, u64, u64p]),
         "fhh_export_keys_bincode": (i, [vp, u64, u64, u64, u8p, u64, u64p]),
+        "fhh_export_timing": (i, [vp, P(ctypes.c_double)]),
         "fhh_num_clients": (i, [vp, u64p]),
         "fhh_export_keys": (i, [vp, u8p, u8p, u8p, u8p]),
         "fhh_tree_init": (i, [vp]),

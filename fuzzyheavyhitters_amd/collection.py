@@ -576,6 +576,47 @@ def gen_keys_ball(c0: KeyCollection, c1: KeyCollection, points: np.ndarray, ball
     del keep
 
 
+def leader_requests_plan(n_dims: int, data_len: int, n: int):
+    """fhh_leader_requests_plan (host arithmetic, no GPU): (items, waves, trips) of the fused leader kernel's launch
+    for n clients — the work items, the waves the launch gets, the trips of its grid-stride loop."""
+    items, waves, trips = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
+    check(lib().fhh_leader_requests_plan(n_dims, data_len, n, ctypes.byref(items), ctypes.byref(waves),
+                                         ctypes.byref(trips)))
+    return items.value, waves.value, trips.value
+
+
+def leader_requests_ball(c: KeyCollection, points: np.ndarray, ball: int, form: str = "bits", root_seeds=None,
+                         seed=None, seed_first: int = 0, batch: int = 0, device_output: bool = False, out=None):
+    """The leader's whole step in one call (leader.rs:130-163, 391-415): the points' keys made and serialized by
+    one kernel into both servers' `add_keys` requests of `batch` clients (0: one request), with no key storage:
+    `c` gives the device and the shape and is otherwise unchanged (it may be empty, or in the middle of a crawl).
+    The bytes are those of `gen_keys_ball` + `export_keys_bincode(0, n, batch)` on each server's collection.
+    Returns two uint8 arrays (server 0, server 1), each the requests back to back — into `out` = (out0, out1),
+    uint8 arrays of at least that size, where given. With device_output: (ptr0, ptr1, nbytes), the addresses of
+    the two request buffers in `c`'s device memory as integers, as the party ABI hands out its device messages;
+    they are valid until the next such call on `c`, its reset or close."""
+    src, n, keep = _ball_src(points, ball, form, c.n_dims, c.depth, root_seeds, seed, seed_first)
+    if device_output:
+        p0, p1, nbytes = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_uint64()
+        check(lib().fhh_leader_requests_ball_device(c.handle, n, ctypes.byref(src), batch, ctypes.byref(p0),
+                                                    ctypes.byref(p1), ctypes.byref(nbytes)), c.handle)
+        del keep
+        return p0.value, p1.value, nbytes.value
+    got = ctypes.c_uint64()
+    if out is None:
+        need = ctypes.c_uint64()
+        if n:   # n = 0 is the library's to refuse
+            check(lib().fhh_bincode_request_bytes(c.n_dims, c.depth, n, batch, ctypes.byref(need)))
+        out = np.empty(need.value, np.uint8), np.empty(need.value, np.uint8)
+    out0, out1 = out
+    if out0.dtype != np.uint8 or out1.dtype != np.uint8 or out0.ndim != 1 or out1.ndim != 1:
+        raise FhhError("leader_requests_ball: out must be two one-dimensional uint8 arrays")
+    check(lib().fhh_leader_requests_ball(c.handle, n, ctypes.byref(src), batch, ptr(out0), ptr(out1),
+                                         min(out0.size, out1.size), ctypes.byref(got)), c.handle)
+    del keep
+    return out0[:got.value], out1[:got.value]
+
+
 def sim_eq_count(c0: KeyCollection, c1: KeyCollection, C: int) -> np.ndarray:
     out = np.zeros(C, np.uint64)
     check(lib().fhh_sim_eq_count(c0.handle, c1.handle, ptr(out, u64p)), c0.handle)
@@ -594,4 +635,5 @@ def sim_ot_sums(c0: KeyCollection, c1: KeyCollection, C: int, prf_seed: int, las
     return [int(x) for x in a], [int(x) for x in b]
 
 
-__all__ = ["KeyCollection", "Result", "gen_keys_pair", "gen_keys_ball", "ball_bounds", "sim_eq_count", "sim_ot_sums", "FE_P", "FE255_P"]
+__all__ = ["KeyCollection", "Result", "gen_keys_pair", "gen_keys_ball", "ball_bounds", "leader_requests_ball",
+           "leader_requests_plan", "sim_eq_count", "sim_ot_sums", "FE_P", "FE255_P"]

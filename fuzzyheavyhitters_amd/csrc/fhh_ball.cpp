@@ -4,6 +4,8 @@
 // point (ball_src.h) and the root seeds are drawn there from a ChaCha20 stream, so a call moves the points (64 B
 // per (client, dim) at L = 512) where fhh_gen_keys_pair moves 2 L bytes of bounds and 64 of seeds.
 // fhh_ball_bounds is the same arithmetic on the host, with no GPU: what the device path means.
+// fhh_leader_requests_ball(_device) takes the same points straight to both servers' add_keys request bytes
+// (k_leader_requests, fhh_leader_requests.hip): the keygen fused with row f5's serialization, no keys stored.
 #include "fhh_engine.h"
 
 #include <cstring>
@@ -114,6 +116,86 @@ int gen_keys_ball_run(fhh_ctx* c0, fhh_ctx* c1, uint64_t n, const fhh_ball_src* 
 
 }  // namespace
 
+// ---- fhh_leader_requests_ball (row i): the same points straight to both servers' add_keys request bytes, made by
+// k_leader_requests (fhh_leader_requests.hip) in buffers of the call's own; no key buffer, phase, frontier or
+// scratch of the ctx is touched, so the call may come on an empty ctx or between the levels of a crawl --------
+static int leader_requests_check(fhh_ctx* ctx, uint64_t n, const fhh_ball_src* src, uint64_t batch, uint64_t* bytes) {
+    std::string why;
+    if (!ball_src_check(ctx->d, ctx->L, n, src, &why)) return ctx->fail(FHH_E_ARG, "leader_requests_ball: " + why);
+    if (n == 0) return ctx->fail(FHH_E_ARG, "leader_requests_ball: no clients (an empty request is refused by the decoder too)");
+    const uint64_t R = be_record_bytes(ctx->d, ctx->L), B = be_batch(n, batch);
+    if (n > (~0ull - 8 * be_requests(n, B)) / R) return ctx->fail(FHH_E_ARG, "leader_requests_ball: size overflows");
+    *bytes = be_total_bytes(n, B, R);
+    return FHH_OK;
+}
+
+// The m clients of `src` (its points, root seeds and seed_first already those of the slice) as clients
+// [i0, i0 + m) of an export of `count` clients in requests of B: their bytes [be_slice_begin(i0),
+// be_slice_end(i0, m)) of both servers' requests, made in ctx->lr_out[b] from byte (be_slice_begin(i0) & ~3) of
+// the export on. Returns when the kernel has run; a carry out is FHH_E_ARG naming client i0 + its index.
+int leader_requests_make(fhh_ctx* ctx, uint64_t m, const fhh_ball_src* src, uint64_t i0, uint64_t count, uint64_t B) {
+    int rc = ctx_set_device(ctx);
+    if (rc) return rc;
+    const size_t d = ctx->d, L = ctx->L;
+    const uint64_t R = be_record_bytes(ctx->d, ctx->L);
+    const uint64_t lo = be_slice_begin(i0, B, R), hi = be_slice_end(i0, m, B, R), org = lo & ~3ull;
+    const size_t pb = m * d * point_bytes(src->form, (uint32_t)L), p_off = 16, r_off = p_off + ((pb + 15) & ~(size_t)15);
+    HIP_TRY(ctx, ctx->lr_stage.ensure(r_off + (src->root_seeds ? m * d * 64 : 0)));
+    for (auto& b : ctx->lr_out) HIP_TRY(ctx, b.ensure(hi - org));
+    uint8_t* st = ctx->lr_stage.as<uint8_t>();
+    HIP_TRY(ctx, hipMemsetAsync(st, 0xFF, 8, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(st + p_off, src->points, pb, hipMemcpyHostToDevice, ctx->stream));
+    if (src->root_seeds)
+        HIP_TRY(ctx, hipMemcpyAsync(st + r_off, src->root_seeds, m * d * 64, hipMemcpyHostToDevice, ctx->stream));
+    LeaderReqArgs a{};
+    a.points = st + p_off;
+    a.root_seeds = src->root_seeds ? st + r_off : nullptr;
+    a.bad = reinterpret_cast<unsigned long long*>(st);
+    for (int b = 0; b < 2; b++) a.out[b] = ctx->lr_out[b].as<uint8_t>();
+    a.org = org;
+    a.n = m;
+    a.i0 = i0;
+    a.count = count;
+    a.B = B;
+    a.d = (uint32_t)d;
+    a.L = (uint32_t)L;
+    a.ball = src->ball;
+    seed_words(src->seed, a.seed);
+    a.seed_first = src->seed_first;
+    hipEvent_t e0, e1;
+    HIP_TRY(ctx, hipEventCreate(&e0));
+    HIP_TRY(ctx, hipEventCreate(&e1));
+    HIP_TRY(ctx, hipEventRecord(e0, ctx->stream));
+    HIP_TRY(ctx, launch_leader_requests(a, src->form == FHH_BALL_BITS ? kKeygenBallBits : kKeygenCoords, ctx->stream));
+    HIP_TRY(ctx, hipEventRecord(e1, ctx->stream));
+    uint64_t bad = ~0ull;
+    HIP_TRY(ctx, hipMemcpyAsync(&bad, st, 8, hipMemcpyDeviceToHost, ctx->stream));
+    // the stream alone: timing events and pinned staging of a crawl in progress stay pending
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    float ms = 0.f;
+    (void)hipEventElapsedTime(&ms, e0, e1);
+    (void)hipEventDestroy(e0);
+    (void)hipEventDestroy(e1);
+    if (bad != ~0ull)
+        return ctx->fail(FHH_E_ARG, "leader_requests_ball: " + carry_text(bad + i0 * d, (uint32_t)d, (uint32_t)L));
+    ctx->stats.keygen_ms += ms;
+    return FHH_OK;
+}
+
+// the bytes leader_requests_make left for clients [i0, i0 + m), to the same offsets of out0 / out1
+int leader_requests_copy(fhh_ctx* ctx, uint64_t m, uint64_t i0, uint64_t B, uint8_t* out0, uint8_t* out1) {
+    int rc = ctx_set_device(ctx);
+    if (rc) return rc;
+    const uint64_t R = be_record_bytes(ctx->d, ctx->L);
+    const uint64_t lo = be_slice_begin(i0, B, R), hi = be_slice_end(i0, m, B, R), org = lo & ~3ull;
+    uint8_t* out[2] = {out0, out1};
+    for (int b = 0; b < 2; b++)
+        HIP_TRY(ctx, hipMemcpyAsync(out[b] + lo, ctx->lr_out[b].as<uint8_t>() + (lo - org), hi - lo, hipMemcpyDeviceToHost,
+                                    ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return FHH_OK;
+}
+
 int gen_keys_ball_one(fhh_ctx* c0, fhh_ctx* c1, uint64_t n, const fhh_ball_src* src, uint64_t client_off) {
     if (c0->device != c1->device || c0->d != c1->d || c0->L != c1->L)
         return c0->fail(FHH_E_ARG, "gen_keys_ball: ctxs differ in device/d/L");
@@ -141,6 +223,53 @@ int fhh_gen_keys_ball(fhh_ctx* c0, fhh_ctx* c1, uint64_t n, const fhh_ball_src* 
     }
     if (c0->group || c1->group) return group_gen_keys_ball(c0, c1, n, src);
     return gen_keys_ball_one(c0, c1, n, src, 0);
+}
+
+int fhh_leader_requests_plan(uint32_t n_dims, uint32_t data_len, uint64_t n, uint64_t* items, uint64_t* waves,
+                             uint64_t* trips) {
+    if (n_dims < 1 || n_dims > (uint32_t)kMaxDims || data_len == 0 || n == 0) {
+        g_err = "leader_requests_plan: n_dims outside 1..4, data_len = 0 or n = 0";
+        return FHH_E_ARG;
+    }
+    const LeaderReqPlan p = leader_req_plan(n_dims, n);
+    if (items) *items = p.items;
+    if (waves) *waves = p.waves;
+    if (trips) *trips = p.trips;
+    return FHH_OK;
+}
+
+int fhh_leader_requests_ball_device(fhh_ctx* ctx, uint64_t n, const fhh_ball_src* src, uint64_t batch,
+                                    const uint8_t** req0_dev, const uint8_t** req1_dev, uint64_t* bytes) {
+    CTX_CHECK(ctx);
+    if (ctx->group)
+        return ctx->fail(FHH_E_ARG, "leader_requests_ball_device: a multi-device ctx has no one device to hand "
+                                    "buffers out on (fhh_shard_ctx, or the host-output form)");
+    if (!req0_dev || !req1_dev || !bytes) return ctx->fail(FHH_E_ARG, "leader_requests_ball_device: NULL output");
+    uint64_t len = 0;
+    int rc = leader_requests_check(ctx, n, src, batch, &len);
+    if (rc) return rc;
+    rc = leader_requests_make(ctx, n, src, 0, n, be_batch(n, batch));
+    if (rc) return rc;
+    *req0_dev = ctx->lr_out[0].as<uint8_t>();
+    *req1_dev = ctx->lr_out[1].as<uint8_t>();
+    *bytes = len;
+    return FHH_OK;
+}
+
+int fhh_leader_requests_ball(fhh_ctx* ctx, uint64_t n, const fhh_ball_src* src, uint64_t batch, uint8_t* out0,
+                             uint8_t* out1, uint64_t cap, uint64_t* len) {
+    CTX_CHECK(ctx);
+    if (!len) return ctx->fail(FHH_E_ARG, "leader_requests_ball: NULL len");
+    int rc = leader_requests_check(ctx, n, src, batch, len);
+    if (rc) return rc;
+    if (!out0 || !out1) return ctx->fail(FHH_E_ARG, "leader_requests_ball: NULL out");
+    if (cap < *len)
+        return ctx->fail(FHH_E_ARG, "leader_requests_ball: " + std::to_string(*len) + " bytes needed, cap " + std::to_string(cap));
+    if (ctx->group) return group_leader_requests_ball(ctx, n, src, batch, out0, out1);
+    const uint64_t B = be_batch(n, batch);
+    rc = leader_requests_make(ctx, n, src, 0, n, B);
+    if (rc) return rc;
+    return leader_requests_copy(ctx, n, 0, B, out0, out1);
 }
 
 int fhh_ball_bounds(uint32_t n_dims, uint32_t data_len, uint64_t n, const fhh_ball_src* src, uint8_t* left_bits,

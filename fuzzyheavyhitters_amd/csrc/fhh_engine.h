@@ -149,6 +149,10 @@ struct fhh_ctx {
     uint64_t reserved = 0;        // fhh_reserve_clients (0: none)
     DevBuf app_buf, app_err;      // a batch's payload and its error word, kept from call to call
     DevBuf emit_buf;              // fhh_export_keys_bincode: the serialized requests, kept from call to call
+    double emit_ms = 0;           // the emit kernels' time (HIP events) of the last export here (fhh_export_timing)
+    // fhh_leader_requests_ball(_device): the two servers' request bytes (handed out by the device form, valid
+    // until the next such call, fhh_reset or fhh_destroy) and the call's [carry word | points | root seeds]
+    DevBuf lr_out[2], lr_stage;
     // the last fhh_retain_clients that ran its kernels here: column / plane gather time (HIP events) and the
     // bytes they read plus wrote (fhh_retain_timing)
     double retain_ms[2] = {0, 0};
@@ -410,6 +414,14 @@ int group_gen_keys_ball(fhh_ctx* g0, fhh_ctx* g1, uint64_t n, const fhh_ball_src
 // of a source for a collection of d dims and L levels
 int gen_keys_ball_one(fhh_ctx* c0, fhh_ctx* c1, uint64_t n, const fhh_ball_src* src, uint64_t client_off);
 bool ball_src_check(uint32_t d, uint32_t L, uint64_t n, const fhh_ball_src* src, std::string* why);
+// fhh_ball.cpp: fhh_leader_requests_ball on one GPU, in the steps a multi-device ctx drives per shard: the m
+// clients of `src` made on ctx's GPU as clients [i0, i0 + m) of an export of `count` clients in requests of B
+// (returns when the kernel has run; a carry out is refused naming client i0 + its index), then their bytes
+// copied to the same offsets of out0 / out1
+int leader_requests_make(fhh_ctx* ctx, uint64_t m, const fhh_ball_src* src, uint64_t i0, uint64_t count, uint64_t B);
+int leader_requests_copy(fhh_ctx* ctx, uint64_t m, uint64_t i0, uint64_t B, uint8_t* out0, uint8_t* out1);
+int group_leader_requests_ball(fhh_ctx* g, uint64_t n, const fhh_ball_src* src, uint64_t batch, uint8_t* out0,
+                               uint8_t* out1);
 int group_num_clients(const fhh_ctx* g, uint64_t* n);
 int group_export_keys(fhh_ctx* g, uint8_t* key_idx, uint8_t* root_seed, uint8_t* cw_seed, uint8_t* cw_bits);
 int group_export_keys_bincode(fhh_ctx* g, uint64_t first, uint64_t count, uint64_t batch, uint8_t* out, uint64_t cap,

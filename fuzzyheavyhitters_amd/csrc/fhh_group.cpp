@@ -382,6 +382,42 @@ int group_gen_keys_ball(fhh_ctx* g0, fhh_ctx* g1, uint64_t n, const fhh_ball_src
     return FHH_OK;
 }
 
+// fhh_leader_requests_ball on a multi-device ctx: the call's n clients are cut by fhh_shard_plan(n, shards) —
+// its own cut, whatever the collection holds — and shard k makes its clients' byte range of both servers'
+// requests on its own GPU, drawing root seeds at seed_first + its first client. Nothing is copied to the host
+// until every shard has made its bytes, so a carry out anywhere leaves out0 / out1 unwritten; the shards are
+// reported in order, so the client named is the population's lowest. A request that straddles two shards has its
+// u64 m written by the shard of its first client.
+int group_leader_requests_ball(fhh_ctx* g, uint64_t n, const fhh_ball_src* src, uint64_t batch, uint8_t* out0,
+                               uint8_t* out1) {
+    Group& G = *g->group;
+    const size_t S = G.shards.size();
+    std::vector<uint64_t> base(S), cnt(S);
+    int rc = fhh_shard_plan(n, (int)S, base.data(), cnt.data());
+    if (rc) return g->fail(rc, "leader_requests_ball: " + g_err);
+    const uint64_t B = be_batch(n, batch);
+    const size_t row = (size_t)g->d * (src->form == FHH_BALL_BITS ? (g->L + 7) / 8 : 2), dR = (size_t)g->d * 64;
+    auto each = [&](auto f) {   // f(k) on one host thread per shard with clients; the first failure in shard order
+        std::vector<int> rcs(S, 0);
+        std::vector<std::thread> th;
+        for (size_t k = 0; k < S; k++)
+            if (cnt[k]) th.emplace_back([&, k] { rcs[k] = f(k); });
+        for (auto& t : th) t.join();
+        for (size_t k = 0; k < S; k++)
+            if (rcs[k]) return shard_fail(g, k, rcs[k]);
+        return (int)FHH_OK;
+    };
+    rc = each([&](size_t k) {
+        fhh_ball_src part = *src;
+        part.points = static_cast<const uint8_t*>(src->points) + base[k] * row;
+        if (src->root_seeds) part.root_seeds = src->root_seeds + base[k] * dR;
+        part.seed_first = src->seed_first + base[k];
+        return leader_requests_make(G.shards[k], cnt[k], &part, base[k], n, B);
+    });
+    if (rc) return rc;
+    return each([&](size_t k) { return leader_requests_copy(G.shards[k], cnt[k], base[k], B, out0, out1); });
+}
+
 int group_num_clients(const fhh_ctx* g, uint64_t* n) {
     const Group& G = *g->group;
     uint64_t v = g->h_n;

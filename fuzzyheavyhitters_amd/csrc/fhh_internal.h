@@ -403,6 +403,38 @@ hipError_t launch_bincode_emit(const uint4* cw_seed, const uint64_t* cw_bits, co
                                const uint64_t* key_idx, uint32_t d, uint32_t L, uint32_t npad, uint32_t nw,
                                uint64_t src_first, uint64_t m, uint64_t i0, uint64_t count, uint64_t B, uint8_t* stg,
                                uint64_t org, hipStream_t stream);
+// fhh_leader_requests.hip (fhh_leader_requests_ball): k_keygen's point forms with the serialization fused in. The n
+// clients of `points` are clients [i0, i0 + n) of an export of `count` clients in requests of B (bincode_emit.h);
+// byte g of server b's requests goes to out[b][g - org], org % 4 == 0, org <= be_slice_begin(i0), out[b] dword
+// aligned and holding be_slice_end(i0, n) - org bytes. No key buffer is read or written.
+struct LeaderReqArgs {
+    const uint8_t* points;      // as KeygenArgs: kKeygenBallBits [n][d][ceil(L / 8)]; kKeygenCoords int16 [n][2]
+    const uint8_t* root_seeds;  // [n][d][2 side][2 server][16], or NULL = drawn from `seed`
+    unsigned long long* bad;    // lowest c d + j whose right bound carries out of bit L (preset to ~0)
+    uint8_t* out[2];
+    uint64_t org;
+    uint64_t n, i0, count, B;
+    uint32_t d, L, ball;
+    uint32_t seed[8];
+    uint64_t seed_first;        // global index of client 0 of `points` in the seed stream
+};
+// The launch of k_leader_requests (fhh_leader_requests_plan): an item is one wave's 64 clients of one key, as
+// k_keygen's; the items are dealt grid-stride to at most kLeaderReqMaxBlocks workgroups of kExpandThreads
+constexpr uint64_t kLeaderReqMaxBlocks = 4096;
+struct LeaderReqPlan {
+    uint64_t items, waves, trips;
+};
+__host__ __device__ inline LeaderReqPlan leader_req_plan(uint32_t d, uint64_t n) {
+    const uint64_t wpb = kExpandThreads / 64;
+    LeaderReqPlan p;
+    p.items = 2ull * d * ((n + 63) / 64);
+    uint64_t blocks = (p.items + wpb - 1) / wpb;
+    if (blocks > kLeaderReqMaxBlocks) blocks = kLeaderReqMaxBlocks;
+    p.waves = blocks * wpb;
+    p.trips = p.waves ? (p.items + p.waves - 1) / p.waves : 0;
+    return p;
+}
+hipError_t launch_leader_requests(const LeaderReqArgs& a, int src, hipStream_t stream);
 // occupancy-derived persistent grid for k_expand variant on `device`
 int expand_grid(int device, int variant);
 // RCCL all-reduce (sum, u64) on `stream` (fhh_comm.cpp); asynchronous

@@ -201,12 +201,22 @@ int export_bincode_slice(fhh_ctx* ctx, uint64_t src_first, uint64_t m, uint64_t 
     const uint64_t lo = be_slice_begin(i0, B, R), hi = be_slice_end(i0, m, B, R), org = lo & ~3ull;
     HIP_TRY(ctx, ctx->emit_buf.ensure(hi - org));
     uint8_t* stg = ctx->emit_buf.as<uint8_t>();
+    hipEvent_t e0, e1;   // the two emit kernels' time, for fhh_export_timing
+    HIP_TRY(ctx, hipEventCreate(&e0));
+    HIP_TRY(ctx, hipEventCreate(&e1));
+    HIP_TRY(ctx, hipEventRecord(e0, ctx->stream));
     HIP_TRY(ctx, launch_bincode_emit(ctx->cw_seed.as<uint4>(), ctx->cw_bits.as<uint64_t>(), ctx->root_seed.as<uint4>(),
                                      ctx->key_idx.as<uint64_t>(), ctx->d, ctx->L, (uint32_t)ctx->npad, (uint32_t)ctx->nw,
                                      src_first, m, i0, count, B, stg, org, ctx->stream));
+    HIP_TRY(ctx, hipEventRecord(e1, ctx->stream));
     HIP_TRY(ctx, hipMemcpyAsync(out + lo, stg + (lo - org), hi - lo, hipMemcpyDeviceToHost, ctx->stream));
     // the stream alone: timing events and pinned staging of a crawl in progress stay pending
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    float ms = 0.f;
+    (void)hipEventElapsedTime(&ms, e0, e1);
+    (void)hipEventDestroy(e0);
+    (void)hipEventDestroy(e1);
+    ctx->emit_ms = ms;
     return FHH_OK;
 }
 
@@ -226,6 +236,13 @@ int fhh_bincode_request_bytes(uint32_t n_dims, uint32_t data_len, uint64_t count
         return FHH_E_ARG;
     }
     *bytes = be_total_bytes(count, B, R);
+    return FHH_OK;
+}
+
+int fhh_export_timing(const fhh_ctx* ctx, double* ms) {
+    CTX_CHECK(ctx);
+    if (ctx->group || !ms) return const_cast<fhh_ctx*>(ctx)->fail(FHH_E_ARG, "export_timing: a one-GPU ctx and a non-NULL ms");
+    *ms = ctx->emit_ms;
     return FHH_OK;
 }
 

@@ -169,6 +169,47 @@ int fhh_gen_keys_ball(fhh_ctx* ctx0, fhh_ctx* ctx1, uint64_t n, const fhh_ball_s
 int fhh_ball_bounds(uint32_t n_dims, uint32_t data_len, uint64_t n, const fhh_ball_src* src,
                     uint8_t* left_bits, uint8_t* right_bits, uint8_t* root_seeds_out, uint64_t* bad);
 
+/* The leader as the reference has it (leader.rs:130-163, 391-415): it never holds a KeyCollection, it makes each
+ * client's keys and sends them as `add_keys` requests. One call: points in, both servers' request bytes out, no key
+ * storage touched — one kernel restates the keygen level loop and writes every key's serialized bytes (header,
+ * CorWords, the client's u64 d, the request's u64 m) at their place in the two request buffers; the CorWords, which
+ * the two servers share, are composed once and stored twice.
+ *
+ * Meaning: the bytes are exactly those of fhh_gen_keys_ball(c0, c1, n, src) followed by
+ * fhh_export_keys_bincode(c_s, 0, n, batch, ...) for server s — the derived root seeds at counter (seed_first +
+ * c) n_dims + j, given root_seeds, wrapped left bounds included — *bytes = *len =
+ * fhh_bincode_request_bytes(n_dims, data_len, n, batch) per server.
+ *
+ * The ctx gives the device, the stream, n_dims, data_len and the error text, and is otherwise unchanged: keys,
+ * phase, frontier, pending children and party state stay as they were, so the call works on an empty ctx (the
+ * leader's case) and on one in the middle of a crawl. The kernel's time is added to stats.keygen_ms.
+ *
+ * fhh_leader_requests_ball_device leaves the two request buffers in device memory and hands out their addresses:
+ * buffers of this call's own (no buffer a crawl uses), owned by the ctx, valid until the next fhh_leader_requests_*
+ * call on it, fhh_reset or fhh_destroy. fhh_leader_requests_ball copies the same bytes to out0 / out1 (host
+ * memory, cap bytes each).
+ *
+ * Refusals (FHH_E_ARG) leave the ctx usable, hand out no device pointer and write nothing to out0 / out1:
+ * everything fhh_gen_keys_ball refuses in a source, n = 0, a NULL output, cap below the needed bytes (*len is
+ * still set), and a carry out — found by the kernel; the copy to the host waits for its verdict; the message names
+ * the lowest (client, dim).
+ *
+ * On a multi-device ctx the host-output form cuts the n clients by fhh_shard_plan(n, shards) and each shard makes
+ * its clients' byte range on its own GPU with seed_first + its first client; a request that straddles two shards
+ * has its count written by the shard of its first client; the bytes are those of a one-GPU call. The
+ * device-output form returns FHH_E_ARG there (use fhh_shard_ctx).
+ *
+ * fhh_leader_requests_plan is host arithmetic, no device call (like fhh_retain_plan / fhh_frontier_plan): the
+ * kernel's work items for n clients (one wave's 64 clients of one key: 2 n_dims ceil(n / 64)), the waves its
+ * launch gets and the trips of the grid-stride loop that follow (ceil(items / waves)). Any output may be NULL.
+ * FHH_E_ARG for n = 0, n_dims outside 1..4, data_len = 0. */
+int fhh_leader_requests_plan(uint32_t n_dims, uint32_t data_len, uint64_t n, uint64_t* items, uint64_t* waves,
+                             uint64_t* trips);
+int fhh_leader_requests_ball_device(fhh_ctx* ctx, uint64_t n, const fhh_ball_src* src, uint64_t batch,
+                                    const uint8_t** req0_dev, const uint8_t** req1_dev, uint64_t* bytes);
+int fhh_leader_requests_ball(fhh_ctx* ctx, uint64_t n, const fhh_ball_src* src, uint64_t batch, uint8_t* out0,
+                             uint8_t* out1, uint64_t cap, uint64_t* len);
+
 /* ---- one KeyCollection over several GPUs (north_star) -----------------------
  * KeyCollection::new on n_devices GPUs: one collection whose clients are sharded over the devices
  * (devices[k] may repeat — two shards on one GPU run the same code on a one-GPU box). At
@@ -234,6 +275,10 @@ int fhh_export_keys(fhh_ctx* ctx, uint8_t* key_idx, uint8_t* root_seed, uint8_t*
 int fhh_bincode_request_bytes(uint32_t n_dims, uint32_t data_len, uint64_t count, uint64_t batch, uint64_t* bytes);
 int fhh_export_keys_bincode(fhh_ctx* ctx, uint64_t first, uint64_t count, uint64_t batch, uint8_t* out, uint64_t cap,
                             uint64_t* len);
+/* For diagnostics only (tools/leader_requests_time.py; like fhh_retain_timing, not part of what a server binds):
+ * *ms = the two emit kernels' time (HIP events) of the last fhh_export_keys_bincode slice serialized on this
+ * one-GPU ctx. */
+int fhh_export_timing(const fhh_ctx* ctx, double* ms);
 
 /* ---- crawl ---------------------------------------------------------------------------- */
 
