@@ -6,8 +6,8 @@ include/fhh.h); this package is the host-side mirror of the reference's KeyColle
 """
 from ._lib import FhhError, build, lib
 from .comm import HostedComm, RcclComm, load_rccl
-from .collection import (KeyCollection, Result, ball_bounds, gen_keys_ball, gen_keys_pair, leader_requests_ball,
-                         leader_requests_plan, sim_eq_count, sim_ot_sums)
+from .collection import (KeyAuditError, KeyCollection, Result, audit_plan, audit_probes, ball_bounds, gen_keys_ball,
+                         gen_keys_pair, leader_requests_ball, leader_requests_plan, sim_eq_count, sim_ot_sums)
 from .fields import FE255_P, FE_P
 from .sim import SimResult, sim_crawl
 from .party import TwoPartyResult, two_party_crawl
@@ -16,7 +16,8 @@ from .leader import add_fuzzy_keys
 __all__ = ["FhhError", "build", "lib", "KeyCollection", "Result", "gen_keys_pair", "sim_eq_count", "sim_ot_sums",
            "FE_P", "FE255_P", "SimResult", "sim_crawl",
            "RcclComm", "HostedComm", "load_rccl", "TwoPartyResult", "two_party_crawl", "shard_plan",
-           "gen_keys_ball", "ball_bounds", "add_fuzzy_keys", "leader_requests_ball", "leader_requests_plan"]
+           "gen_keys_ball", "ball_bounds", "add_fuzzy_keys", "leader_requests_ball", "leader_requests_plan",
+           "KeyAuditError", "audit_plan", "audit_probes"]
 
 
 def shard_plan(n_clients: int, n_shards: int):

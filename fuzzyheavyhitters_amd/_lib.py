@@ -64,6 +64,8 @@ EXPORTS = [
     "fhh_gen_keys_ball", "fhh_ball_bounds",
     "fhh_leader_requests_ball", "fhh_leader_requests_ball_device", "fhh_leader_requests_plan",
     "fhh_party_set_server", "fhh_party_role_plan", "fhh_party_negate",
+    "fhh_audit_keys_ball", "fhh_audit_keys_ball_device", "fhh_audit_probes", "fhh_audit_plan", "fhh_audit_timing",
+    "fhh_audit_seed_check",
 ]
 
 
@@ -120,8 +122,9 @@ class FhhSimConfig(ctypes.Structure):
     ]
 
 
-SOURCES = ("fhh_kernels.hip", "fhh_bincode_out.hip", "fhh_leader_requests.hip", "fhh_retain.hip", "fhh_retain_mask.hip", "fhh_sketch.hip", "fhh_gc.hip", "fhh_ot.hip",
+SOURCES = ("fhh_kernels.hip", "fhh_bincode_out.hip", "fhh_leader_requests.hip", "fhh_audit.hip", "fhh_retain.hip", "fhh_retain_mask.hip", "fhh_sketch.hip", "fhh_gc.hip", "fhh_ot.hip",
            "fhh_loop.hip", "fhh_microbench.hip", "fhh_host.cpp", "fhh_keys_io.cpp", "fhh_retain.cpp", "fhh_ball.cpp",
+           "fhh_audit.cpp",
            "fhh_sim_crawl.cpp", "fhh_sketch_host.cpp",
            "fhh_gcot.cpp", "fhh_gcot_harness.cpp", "fhh_group.cpp", "fhh_comm.cpp", "fhh_base_ot.cpp")
 
@@ -139,6 +142,21 @@ class FhhBallSrc(ctypes.Structure):
         ("root_seeds", u8p),
         ("seed", ctypes.c_uint8 * 32),
         ("seed_first", ctypes.c_uint64),
+    ]
+
+
+class FhhAuditReport(ctypes.Structure):
+    """fhh_audit_report: what fhh_audit_keys_ball found (include/fhh.h)."""
+    _fields_ = [
+        ("n_checks", ctypes.c_uint64),
+        ("n_bad_clients", ctypes.c_uint64),
+        ("first_client", ctypes.c_uint64),
+        ("first_dim", ctypes.c_uint32),
+        ("first_side", ctypes.c_uint32),
+        ("first_probe", ctypes.c_uint32),
+        ("first_level", ctypes.c_uint32),
+        ("got", ctypes.c_uint32),
+        ("expected", ctypes.c_uint32),
     ]
 
 
@@ -344,6 +362,12 @@ def lib():
         "fhh_leader_requests_plan": (i, [u32, u32, u64, u64p, u64p, u64p]),
         "fhh_leader_requests_ball_device": (i, [vp, u64, P(FhhBallSrc), u64, P(vp), P(vp), u64p]),
         "fhh_leader_requests_ball": (i, [vp, u64, P(FhhBallSrc), u64, u8p, u8p, u64, u64p]),
+        "fhh_audit_keys_ball": (i, [vp, vp, u64, P(FhhBallSrc), u8p, P(FhhAuditReport)]),
+        "fhh_audit_keys_ball_device": (i, [vp, vp, u64, P(FhhBallSrc), P(vp), P(FhhAuditReport)]),
+        "fhh_audit_probes": (i, [u32, u32, u64, P(FhhBallSrc), u8p, u64p]),
+        "fhh_audit_plan": (i, [u32, u32, u64, u64, u64p, u64p, u64p, u64p, u64p, u64p]),
+        "fhh_audit_timing": (i, [vp, P(ctypes.c_double)]),
+        "fhh_audit_seed_check": (i, [vp, u64p]),
         "fhh_add_keys_bincode": (i, [vp, u8p, u64]),
         "fhh_reserve_clients": (i, [vp, u64]),
         "fhh_add_keys_bincode_append": (i, [vp, u8p, u64]),

@@ -9,7 +9,8 @@ from dataclasses import dataclass
 
 import numpy as np
 
-from ._lib import FHH_BALL_BITS, FHH_BALL_COORDS, FhhBallSrc, FhhError, FhhStats, check, lib, ptr, u32p, u64p
+from ._lib import (FHH_BALL_BITS, FHH_BALL_COORDS, FhhAuditReport, FhhBallSrc, FhhError, FhhStats, check, lib, ptr, u32p,
+                   u64p)
 from .fields import FE255_P, FE_P, limbs10_to_int, int_to_limbs
 
 
@@ -60,6 +61,33 @@ def _device_mask(keep, n, n_rows, row_stride):
         raise FhhError("keep mask: row stride below the row length")
     torch.cuda.synchronize(keep.device)   # the library reads on its own stream: torch's writes must be complete
     return ctypes.c_void_p(keep.data_ptr()), int(cols), int(rows), int(stride)
+
+
+class KeyAuditError(FhhError):
+    """Keys that do not mean what their points say (`leader.add_fuzzy_keys(audit=True)`): `report` is the audit's
+    report (`KeyCollection.audit_keys_ball`), `ok` its per-client bytes, `first` the population index of the audited
+    chunk's client 0."""
+
+    def __init__(self, report: dict, ok: np.ndarray, first: int = 0):
+        self.report, self.ok, self.first = report, ok, first
+        super().__init__(f"key audit: {report['n_bad_clients']} of {ok.size} clients from client {first} on fail; first "
+                         f"client {report['first_client']} dim {report['first_dim']} side {report['first_side']} probe "
+                         f"{report['first_probe']} level {report['first_level']}: got {report['got']}, expected "
+                         f"{report['expected']}")
+
+
+def _audit_report(rep: FhhAuditReport, c: "KeyCollection") -> dict:
+    """fhh_audit_report as a dict (first_client None when every client is ok), with the diagnostics of the call:
+    the kernel's time and the walks whose seeds diverged (fhh_audit_timing, fhh_audit_seed_check)."""
+    out = {name: int(getattr(rep, name)) for name, _ in FhhAuditReport._fields_}
+    if out["first_client"] == 2 ** 64 - 1:
+        out["first_client"] = None
+    ms, div = ctypes.c_double(), ctypes.c_uint64()
+    check(lib().fhh_audit_timing(c.handle, ctypes.byref(ms)), c.handle)
+    check(lib().fhh_audit_seed_check(c.handle, ctypes.byref(div)), c.handle)
+    out["kernel_ms"] = ms.value
+    out["seed_diverged"] = int(div.value)
+    return out
 
 
 class KeyCollection:
@@ -199,6 +227,38 @@ class KeyCollection:
         self._chk(lib().fhh_export_keys_bincode(self._h, first, count, batch, ptr(out), out.size, ctypes.byref(got)))
         assert got.value == out.size
         return out
+
+    def audit_keys_ball(self, other: "KeyCollection", points: np.ndarray, ball: int, form: str = "bits"):
+        """Do the keys mean what the points say (fhh_audit_keys_ball)? self holds server 0's keys, `other` server
+        1's, of the clients whose `points` (in `gen_keys_ball`'s layout for `form`) and `ball` made them. Both
+        servers' keys of every client are evaluated on the GPU at the probes l - 1, l, a, r, r + 1 of each dim
+        and, after every level, the reconstructed bit is compared with the interval rule. Returns (ok, report):
+        ok uint8 [n], 1 for a client whose comparisons all hold; report a dict of fhh_audit_report's fields
+        (first_client None when all are ok) plus kernel_ms and seed_diverged. The collections are otherwise
+        unchanged: the call may come between the levels of a crawl. A failed audit is a result, not an error."""
+        src, n, keep = _ball_src(points, ball, form, self.n_dims, self.depth, None, bytes(32), 0)
+        ok = np.zeros(n, np.uint8)
+        rep = FhhAuditReport()
+        self._chk(lib().fhh_audit_keys_ball(self._h, other.handle, n, ctypes.byref(src), ptr(ok) if n else None,
+                                            ctypes.byref(rep)))
+        del keep
+        return ok, _audit_report(rep, self)
+
+    def audit_keys_ball_device(self, other: "KeyCollection", points: np.ndarray, ball: int, form: str = "bits"):
+        """`audit_keys_ball` with the ok bytes left in device memory (fhh_audit_keys_ball_device; one-GPU
+        collections only): (ok, report) with ok a torch.uint8 tensor [n] on this collection's GPU, a copy of the
+        library's buffer made on the device, usable as a mask (row) of `retain_clients_device`."""
+        import torch
+        src, n, keep = _ball_src(points, ball, form, self.n_dims, self.depth, None, bytes(32), 0)
+        p = ctypes.c_void_p()
+        rep = FhhAuditReport()
+        self._chk(lib().fhh_audit_keys_ball_device(self._h, other.handle, n, ctypes.byref(src), ctypes.byref(p),
+                                                   ctypes.byref(rep)))
+        del keep
+        ok = torch.empty(n, dtype=torch.uint8, device=f"cuda:{self.device}")
+        torch.cuda.synchronize(self.device)
+        check(lib().fhh_memcpy_device(self.device, ctypes.c_void_p(ok.data_ptr()), p, n))
+        return ok, _audit_report(rep, self)
 
     def retain_clients(self, keep):
         """`apply_sketch_results` (main.rs:68-69): drop the clients whose keep entry is false (fhh_retain_clients).
@@ -574,6 +634,27 @@ def gen_keys_ball(c0: KeyCollection, c1: KeyCollection, points: np.ndarray, ball
     src, n, keep = _ball_src(points, ball, form, c0.n_dims, c0.depth, root_seeds, seed, seed_first)
     check(lib().fhh_gen_keys_ball(c0.handle, c1.handle, n, ctypes.byref(src)), c0.handle)
     del keep
+
+
+def audit_plan(n_dims: int, data_len: int, n: int, grid_blocks: int) -> dict:
+    """fhh_audit_plan (host arithmetic, no GPU): the audit kernel's launch for n clients on at most grid_blocks
+    workgroups — items, waves, trips of the grid-stride loop, last_trip_items, aes_blocks, n_checks."""
+    names = ("items", "waves", "trips", "last_trip_items", "aes_blocks", "n_checks")
+    v = [ctypes.c_uint64() for _ in names]
+    check(lib().fhh_audit_plan(n_dims, data_len, n, grid_blocks, *[ctypes.byref(x) for x in v]))
+    return {k: int(x.value) for k, x in zip(names, v)}
+
+
+def audit_probes(points: np.ndarray, ball: int, *, n_dims: int, data_len: int, form: str = "bits") -> np.ndarray:
+    """fhh_audit_probes (host arithmetic, no GPU): the audit's probes l - 1, l, a, r, r + 1 mod 2^L of every
+    (client, dim) as uint8 [n][d][5][L], a byte per bit, MSB first. Raises on a carry out, naming the lowest
+    (client, dim)."""
+    src, n, keep = _ball_src(points, ball, form, n_dims, data_len, None, bytes(32), 0)
+    out = np.zeros((n, n_dims, 5, data_len), np.uint8)
+    bad = ctypes.c_uint64()
+    check(lib().fhh_audit_probes(n_dims, data_len, n, ctypes.byref(src), ptr(out), ctypes.byref(bad)))
+    del keep
+    return out
 
 
 def leader_requests_plan(n_dims: int, data_len: int, n: int):

@@ -1,7 +1,8 @@
 // The leader's gen_l_inf_ball (ibDCF.rs:175-188) and gen_l_inf_ball_from_coords (ibDCF.rs:189-205) as arithmetic
 // on a client's point: the bits of the two interval bounds that gen_interval (ibDCF.rs:138-173) keys, and the root
-// seeds of a (client, dim) from a seed stream. One copy for the host (fhh_ball_bounds, fhh_ball.cpp) and for
-// k_keygen's point forms (fhh_kernels.hip), so what the CPU tests hold is what the kernel computes.
+// seeds of a (client, dim) from a seed stream. One copy for the host (fhh_ball_bounds, fhh_ball.cpp;
+// fhh_audit_probes, fhh_audit.cpp) and for k_keygen's point forms (fhh_kernels.hip), k_leader_requests and k_audit_keys,
+// so what the CPU tests hold is what the kernels compute.
 //
 // BITS form. A point is an L-bit string a, MSB first, packed 8 bits per byte (string bit l = bit 7 - l % 8 of byte
 // l / 8). delta = MSB_u32_to_bits(32, size) (ibDCF.rs:178) is 32 bits wide and L >= 32, so
@@ -82,17 +83,9 @@ struct BallBound {
     bool carry_out;       // right bound only: a + delta >= 2^L
 };
 
-// One bound of the point in `row`: right = a + delta, left = a - delta mod 2^L. Reads the row's low word and,
-// where a carry or borrow leaves it, the words its run crosses (one word in all but 2^-32 of uniform points).
-__host__ __device__ inline BallBound ball_bound(const uint8_t* row, uint32_t L, uint32_t delta, bool right) {
-    const uint32_t nb = (L + 7) >> 3;
-    const uint32_t a = ball_str32(row, nb, L - 32);
-    BallBound r;
-    r.low = right ? a + delta : a - delta;
-    r.flip_from = 0xFFFFFFFFu;
-    r.carry_out = false;
-    const bool cb = right ? r.low < a : a < delta;
-    if (!cb) return r;
+// The length t of the run that a carry (right) or a borrow out of the low word crosses: the ones (zeros) of the
+// string bits L - 33, L - 34, ... up to the first zero (one); t = L - 32 where the run reaches the top.
+__host__ __device__ inline uint32_t ball_run(const uint8_t* row, uint32_t nb, uint32_t L, bool right) {
     uint32_t hi = L - 32, t = 0;   // the run so far is the string bits hi .. L - 33
     while (hi) {
         const uint32_t cnt = hi < 32 ? hi : 32;
@@ -106,9 +99,49 @@ __host__ __device__ inline BallBound ball_bound(const uint8_t* row, uint32_t L, 
         t += cnt;
         hi -= cnt;
     }
+    return t;
+}
+
+// One bound of the point in `row`: right = a + delta, left = a - delta mod 2^L. Reads the row's low word and,
+// where a carry or borrow leaves it, the words its run crosses (one word in all but 2^-32 of uniform points).
+__host__ __device__ inline BallBound ball_bound(const uint8_t* row, uint32_t L, uint32_t delta, bool right) {
+    const uint32_t nb = (L + 7) >> 3;
+    const uint32_t a = ball_str32(row, nb, L - 32);
+    BallBound r;
+    r.low = right ? a + delta : a - delta;
+    r.flip_from = 0xFFFFFFFFu;
+    r.carry_out = false;
+    const bool cb = right ? r.low < a : a < delta;
+    if (!cb) return r;
+    const uint32_t t = ball_run(row, nb, L, right);
     r.carry_out = right && t == L - 32;
     r.flip_from = t >= L - 33 ? 0u : L - 33 - t;   // the run and the bit above it; a wrap flips them all
     return r;
+}
+
+// ---- the audit's probes (fhh_audit_keys_ball, fhh_audit_probes): x_p = l - 1, l, a, r, r + 1 mod 2^L for
+// p = 0 .. 4, the points at and around the bounds at which a key pair is evaluated. In the BITS form x_p = a -/+ m
+// with m = delta + 1, delta, 0: m has 33 bits at delta = 2^32 - 1, where the low word is the point's own and the
+// carry (borrow) into bit 32 is certain. A probe wraps where a bound would carry out (each key is judged alone);
+// carry_out still reports it, for p = 3 (the right bound itself).
+constexpr uint32_t kAuditProbes = 5;
+__host__ __device__ inline BallBound ball_offset(const uint8_t* row, uint32_t L, uint64_t m, bool right) {
+    const uint32_t nb = (L + 7) >> 3;
+    const uint32_t a = ball_str32(row, nb, L - 32), lo = (uint32_t)m;
+    BallBound r;
+    r.low = right ? a + lo : a - lo;
+    r.flip_from = 0xFFFFFFFFu;
+    r.carry_out = false;
+    const bool cb = (m >> 32) != 0 || (right ? r.low < a : a < lo);
+    if (!cb) return r;
+    const uint32_t t = ball_run(row, nb, L, right);
+    r.carry_out = right && t == L - 32;
+    r.flip_from = t >= L - 33 ? 0u : L - 33 - t;
+    return r;
+}
+__host__ __device__ inline BallBound ball_probe(const uint8_t* row, uint32_t L, uint32_t delta, uint32_t p) {
+    const uint64_t m = p == 2 ? 0ull : (uint64_t)delta + ((p == 0 || p == 4) ? 1u : 0u);
+    return ball_offset(row, L, m, p > 2);
 }
 
 // string bit l of the bound; cur = ball_str32(row, nb, l & ~31u) (unused for l >= L - 32)
@@ -123,6 +156,12 @@ __host__ __device__ inline uint32_t coords_bound(int16_t c, uint32_t j, uint32_t
     int32_t v = right ? (int32_t)c + (int32_t)ball : (int32_t)c - (int32_t)ball;
     v = v < -lim ? -lim : (v > lim ? lim : v);
     return (uint32_t)v & 0xFFFFu;
+}
+// probe p of dim j: the bounds' 16-bit patterns -/+ 1 mod 2^16, and the point's own pattern (i16_to_bitvec(c))
+__host__ __device__ inline uint32_t coords_probe(int16_t c, uint32_t j, uint32_t ball, uint32_t p) {
+    if (p == 2) return (uint32_t)c & 0xFFFFu;
+    const uint32_t b = coords_bound(c, j, ball, p > 2);
+    return (p == 0 ? b - 1u : (p == 4 ? b + 1u : b)) & 0xFFFFu;
 }
 
 }  // namespace fhh

@@ -77,14 +77,17 @@ template <class Ops> struct TabT0R32 {
 };
 
 // ---- AES-128 (zero key) + MMO over a table layout ----------------------------------------
+// ff ^= AES_0(in). With ff = in this is the MMO of prg.rs:227-230 (aes0_mmo_tab); a caller that owes the output
+// another XOR (k_audit_keys: the CorWord of a set control bit) hands it in through ff, so that nothing but ff
+// lives through the rounds.
 template <class Ops, class Tab, int NB>
-__host__ __device__ __forceinline__ void aes0_mmo_tab(uint32_t (&s)[NB][4], const uint32_t* tbl, uint32_t b0,
-                                                      uint32_t b1) {
+__host__ __device__ __forceinline__ void aes0_mmo_tab_ff(const uint32_t (&in)[NB][4], uint32_t (&s)[NB][4],
+                                                         const uint32_t* tbl, uint32_t b0, uint32_t b1) {
     uint32_t x[NB][4];
 #pragma unroll
     for (int b = 0; b < NB; b++)
 #pragma unroll
-        for (int c = 0; c < 4; c++) x[b][c] = s[b][c];   // rk0 = 0
+        for (int c = 0; c < 4; c++) x[b][c] = in[b][c];   // rk0 = 0
 #pragma unroll
     for (int r = 1; r < 10; r++) {
         uint32_t y[NB][4];
@@ -120,6 +123,11 @@ __host__ __device__ __forceinline__ void aes0_mmo_tab(uint32_t (&s)[NB][4], cons
 #pragma unroll
         for (int c = 0; c < 4; c++) s[b][c] ^= o[c];   // MMO feed-forward (prg.rs:227-230)
     }
+}
+template <class Ops, class Tab, int NB>
+__host__ __device__ __forceinline__ void aes0_mmo_tab(uint32_t (&s)[NB][4], const uint32_t* tbl, uint32_t b0,
+                                                      uint32_t b1) {
+    aes0_mmo_tab_ff<Ops, Tab, NB>(s, s, tbl, b0, b1);
 }
 
 // ---- AES-128 (zero key) + MMO for sibling counter PAIRS ---------------------------------

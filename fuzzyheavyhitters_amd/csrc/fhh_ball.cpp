@@ -36,14 +36,14 @@ bool ball_src_check(uint32_t d, uint32_t L, uint64_t n, const fhh_ball_src* src,
     return true;
 }
 
-namespace {
-
 size_t point_bytes(uint32_t form, uint32_t L) { return form == FHH_BALL_BITS ? (L + 7) / 8 : 2; }
 
 std::string carry_text(uint64_t idx, uint32_t d, uint32_t L) {
     return "client " + std::to_string(idx / d) + ", dim " + std::to_string(idx % d) + ": point + ball carries out of bit " +
            std::to_string(L) + " (add_bitstrings grows the string and the leader panics, ibDCF.rs:182)";
 }
+
+namespace {
 
 void seed_words(const uint8_t seed[32], uint32_t (&w)[8]) {
     for (int k = 0; k < 8; k++)

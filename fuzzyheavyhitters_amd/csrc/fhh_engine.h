@@ -153,6 +153,12 @@ struct fhh_ctx {
     // fhh_leader_requests_ball(_device): the two servers' request bytes (handed out by the device form, valid
     // until the next such call, fhh_reset or fhh_destroy) and the call's [carry word | points | root seeds]
     DevBuf lr_out[2], lr_stage;
+    // fhh_audit_keys_ball(_device): [record | ok bytes | points] of the last audit with this ctx as ctx0 (the ok
+    // bytes handed out by the device form, valid until the next audit, fhh_reset or fhh_destroy), its kernel time
+    // (HIP events) and its count of walks whose seeds diverged (fhh_audit_timing, fhh_audit_seed_check)
+    DevBuf audit_buf;
+    double audit_ms = 0;
+    uint64_t audit_diverged = 0;
     // the last fhh_retain_clients that ran its kernels here: column / plane gather time (HIP events) and the
     // bytes they read plus wrote (fhh_retain_timing)
     double retain_ms[2] = {0, 0};
@@ -290,6 +296,7 @@ inline std::array<uint32_t, 8> fe255_sub(const std::array<uint32_t, 8>& a, const
     return out;
 }
 int alloc_keys(fhh_ctx* ctx, uint64_t n);   // the key buffers and `valid` of n clients (a one-shot layout)
+int upload_staged(fhh_ctx* ctx);            // keys staged by fhh_add_keys to the device, as tree_init(_at) does
 int finish_appended(fhh_ctx* ctx);          // fhh_keys_io.cpp: tree_init on appended keys
 #pragma GCC visibility pop
 
@@ -422,6 +429,18 @@ int leader_requests_make(fhh_ctx* ctx, uint64_t m, const fhh_ball_src* src, uint
 int leader_requests_copy(fhh_ctx* ctx, uint64_t m, uint64_t i0, uint64_t B, uint8_t* out0, uint8_t* out1);
 int group_leader_requests_ball(fhh_ctx* g, uint64_t n, const fhh_ball_src* src, uint64_t batch, uint8_t* out0,
                                uint8_t* out1);
+// fhh_ball.cpp: bytes of one (client, dim) point of a form, and the text of a carry out at index c d + j
+size_t point_bytes(uint32_t form, uint32_t L);
+std::string carry_text(uint64_t idx, uint32_t d, uint32_t L);
+// fhh_audit.cpp: fhh_audit_keys_ball on one-GPU ctxs. The ok bytes stay in c0->audit_buf (audit_ok_dev) and go to
+// ok_host where given; failures and a carry out are named client_off + their index.
+struct AuditOut {
+    uint64_t n_checks = 0, n_bad = 0, first = ~0ull, diverged = 0;   // first: AuditArgs' packed failure, global client
+};
+int audit_keys_one(fhh_ctx* c0, fhh_ctx* c1, uint64_t n, const fhh_ball_src* src, uint64_t client_off, uint8_t* ok_host,
+                   AuditOut* out);
+int audit_copy_ok(fhh_ctx* c0, uint64_t n, uint8_t* ok_host);   // the ok bytes of c0's last audit, to the host
+int group_audit_keys_ball(fhh_ctx* g0, fhh_ctx* g1, uint64_t n, const fhh_ball_src* src, uint8_t* ok, AuditOut* out);
 int group_num_clients(const fhh_ctx* g, uint64_t* n);
 int group_export_keys(fhh_ctx* g, uint8_t* key_idx, uint8_t* root_seed, uint8_t* cw_seed, uint8_t* cw_bits);
 int group_export_keys_bincode(fhh_ctx* g, uint64_t first, uint64_t count, uint64_t batch, uint8_t* out, uint64_t cap,

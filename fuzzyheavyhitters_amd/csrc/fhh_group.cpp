@@ -505,6 +505,63 @@ static int place_keys(fhh_ctx* g, const char* who) {
     return FHH_OK;
 }
 
+// fhh_audit_keys_ball on multi-device ctxs: shard k of both collections audits its own clients' keys against their
+// slice of the points on its GPU. The ok bytes land at the shard's first client, the counts are summed, and the
+// failures carry global client indices, so the lowest over the shards is the collection's first. A carry out is
+// reported in shard order: the client named is the population's lowest.
+int group_audit_keys_ball(fhh_ctx* g0, fhh_ctx* g1, uint64_t n, const fhh_ball_src* src, uint8_t* ok, AuditOut* out) {
+    Group &G0 = *g0->group, &G1 = *g1->group;
+    if (G0.devices != G1.devices) return g0->fail(FHH_E_ARG, "audit_keys_ball: the two collections differ in devices");
+    int rc = place_keys(g0, "audit_keys_ball");
+    if (rc) return rc;
+    rc = place_keys(g1, "audit_keys_ball");
+    if (rc) return g0->fail(rc, g1->err);
+    uint64_t n0 = 0, n1 = 0;
+    group_num_clients(g0, &n0);
+    group_num_clients(g1, &n1);
+    if (n0 == 0 || n1 == 0) return g0->fail(FHH_E_STATE, "audit_keys_ball: the ctx holds no keys");
+    if (n0 != n || n1 != n)
+        return g0->fail(FHH_E_ARG, "audit_keys_ball: n = " + std::to_string(n) + " but the ctxs hold " + std::to_string(n0) +
+                                       " and " + std::to_string(n1) + " clients");
+    const size_t S = G0.shards.size();
+    for (size_t k = 0; k < S; k++)
+        if (G0.base[k] != G1.base[k] || G0.count[k] != G1.count[k])
+            return g0->fail(FHH_E_ARG, "audit_keys_ball: the two collections are cut differently at shard " + std::to_string(k));
+    const size_t row = (size_t)g0->d * point_bytes(src->form, g0->L);
+    std::vector<AuditOut> outs(S);
+    std::vector<int> rcs(S, 0);
+    std::vector<std::thread> th;
+    for (size_t k = 0; k < S; k++) {
+        if (!G0.count[k]) continue;   // (keys staged by fhh_add_keys are still on the shard's host side: its n is 0)
+        th.emplace_back([&, k] {
+            fhh_ball_src part = *src;
+            part.points = static_cast<const uint8_t*>(src->points) + G0.base[k] * row;
+            rcs[k] = audit_keys_one(G0.shards[k], G1.shards[k], G0.count[k], &part, G0.base[k], nullptr, &outs[k]);
+        });
+    }
+    for (auto& t : th) t.join();
+    for (size_t k = 0; k < S; k++)
+        if (rcs[k]) return shard_fail(g0, k, rcs[k]);
+    // nothing reaches the caller's ok bytes until every shard has its verdict (a carry out anywhere refuses the call)
+    for (size_t k = 0; ok && k < S; k++) {
+        if (!G0.count[k]) continue;
+        rc = audit_copy_ok(G0.shards[k], G0.count[k], ok + G0.base[k]);
+        if (rc) return shard_fail(g0, k, rc);
+    }
+    *out = AuditOut{};
+    g0->audit_ms = 0;
+    for (size_t k = 0; k < S; k++) {
+        if (!G0.count[k]) continue;
+        out->n_checks += outs[k].n_checks;
+        out->n_bad += outs[k].n_bad;
+        out->diverged += outs[k].diverged;
+        out->first = std::min(out->first, outs[k].first);
+        g0->audit_ms = std::max(g0->audit_ms, G0.shards[k]->audit_ms);
+    }
+    g0->audit_diverged = out->diverged;
+    return FHH_OK;
+}
+
 int group_tree_init(fhh_ctx* g) {
     int rc = place_keys(g, "tree_init");
     if (rc) return rc;

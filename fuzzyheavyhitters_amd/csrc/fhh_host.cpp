@@ -295,6 +295,8 @@ int ctx_set_device(fhh_ctx* ctx) {
     return FHH_OK;
 }
 
+int upload_staged(fhh_ctx* ctx) { return upload_staged_keys(ctx); }
+
 int alloc_keys(fhh_ctx* ctx, uint64_t n) {
     ctx->appended = false;   // a one-shot layout replaces an unused reservation
     ctx->reserved = 0;

@@ -435,6 +435,54 @@ __host__ __device__ inline LeaderReqPlan leader_req_plan(uint32_t d, uint64_t n)
     return p;
 }
 hipError_t launch_leader_requests(const LeaderReqArgs& a, int src, hipStream_t stream);
+// fhh_audit.hip (fhh_audit_keys_ball, row j): both servers' keys of every client evaluated at the five probes of
+// its point (ball_src.h) and every prefix's reconstructed bit compared with the interval rule. An item is one
+// wave's 64 clients of one key (dim j, side), lane = client; it walks the 5 probes with both servers' keys, 10
+// AES blocks per level. Each server's keys come in their own layout (an appended collection keeps its capacity
+// stride until tree_init).
+struct AuditSrv {
+    const uint4* cw_seed;
+    const uint64_t* cw_bits;
+    const uint4* root_seed;
+    const uint64_t* key_idx;
+    uint32_t npad, nw;
+};
+// a failure as one u64, ordered as (client, dim, side, probe, level): client << 25 | dim << 23 | side << 22 |
+// probe << 19 | level << 1 | expected bit (level = 1 .. L < 2^18: the prefix length compared)
+constexpr uint32_t kAuditMaxLevels = (1u << 18) - 1;
+constexpr uint32_t kAuditRecWords = 5;
+struct AuditArgs {
+    AuditSrv srv[2];
+    const uint8_t* points;      // as KeygenArgs: kKeygenBallBits [n][d][ceil(L / 8)]; kKeygenCoords int16 [n][2]
+    uint8_t* ok;                // [n], preset to 1: cleared for a client with a failed comparison
+    // [0] the lowest failure (preset to ~0), [1] comparisons made (0), [2] lowest c d + j whose right bound carries
+    // out of bit L (~0), [3] clients with ok = 0 (0; k_audit_count), [4] walks that end off the key's path with the
+    // two servers' seeds unequal (0)
+    unsigned long long* rec;
+    uint64_t n;
+    uint32_t d, L, K, ball;
+};
+// The launch of k_audit_keys (fhh_audit_plan): k_eval_paths' shape, workgroups of kAuditBlock threads, at most
+// `grid_blocks` of them, the items dealt grid-stride
+constexpr int kAuditBlock = 1024;
+struct AuditPlan {
+    uint64_t items, blocks, waves, trips, last_trip_items, aes_blocks, n_checks;
+};
+__host__ __device__ inline AuditPlan audit_plan(uint32_t d, uint32_t L, uint64_t n, uint64_t grid_blocks) {
+    const uint64_t wpb = kAuditBlock / 64;
+    AuditPlan p;
+    p.items = 2ull * d * ((n + 63) / 64);
+    p.blocks = (p.items + wpb - 1) / wpb;
+    if (p.blocks > grid_blocks) p.blocks = grid_blocks;
+    p.waves = p.blocks * wpb;
+    p.trips = p.waves ? (p.items + p.waves - 1) / p.waves : 0;
+    p.last_trip_items = p.trips ? p.items - (p.trips - 1) * p.waves : 0;
+    p.n_checks = n * 2 * d * 5 * L;
+    p.aes_blocks = 2 * p.n_checks;   // both servers' keys at every (probe, level)
+    return p;
+}
+// form: kKeygenBallBits / kKeygenCoords; also counts the cleared ok bytes into rec[3]
+hipError_t launch_audit_keys(const AuditArgs& a, int form, int grid_blocks, hipStream_t stream);
 // occupancy-derived persistent grid for k_expand variant on `device`
 int expand_grid(int device, int variant);
 // RCCL all-reduce (sum, u64) on `stream` (fhh_comm.cpp); asynchronous

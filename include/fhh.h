@@ -210,6 +210,67 @@ int fhh_leader_requests_ball_device(fhh_ctx* ctx, uint64_t n, const fhh_ball_src
 int fhh_leader_requests_ball(fhh_ctx* ctx, uint64_t n, const fhh_ball_src* src, uint64_t batch, uint8_t* out0,
                              uint8_t* out1, uint64_t cap, uint64_t* len);
 
+/* ---- audit (row j): do a population's keys mean what its points say? ---------------------------
+ * The reference's check of one key is eval_ibDCF (ibDCF.rs:238-250) at points around the bounds, as interval_test
+ * and test_individual_dcfs do it (tests/ibdcf_tests.rs). fhh_audit_keys_ball is that check for every client, on
+ * the GPU, with server 0's keys in ctx0 and server 1's in ctx1.
+ *
+ * The rule. For client c and dim j let l and r be the bounds fhh_gen_keys_ball keys from `src` (FHH_BALL_BITS: l =
+ * a - ball mod 2^L, r = a + ball; FHH_BALL_COORDS: the clamped values' 16-bit patterns) and a the point's own
+ * string. The probes are x_p = l - 1, l, a, r, r + 1 mod 2^L for p = 0 .. 4 (a probe may wrap: each key is judged
+ * alone). Each probe is walked from the root through all L levels with both servers' keys (eval_init / eval_bit,
+ * ibDCF.rs:208-236; each ctx's own CorWords), and after every level k = 1 .. L the reconstructed bit e = y0 ^ t0 ^
+ * y1 ^ t1 is compared with [x_p[..k] < l[..k]] for the left key (side 0) and [x_p[..k] > r[..k]] for the right key
+ * (side 1), the top k bits as integers. A client is ok iff all its 2 d 5 L comparisons hold.
+ *
+ * ctx0 / ctx1: on one device, with the same n_dims and data_len (FHH_E_ARG otherwise), both holding n clients
+ * (FHH_E_STATE for a ctx without keys, FHH_E_ARG for another count). Keys may have been staged by fhh_add_keys
+ * (they are uploaded as fhh_tree_init_at uploads them), appended, decoded or made on the device. Phase, frontier,
+ * pending children and party state are untouched: the call is legal between the levels of a crawl. `src` is the
+ * source of the keygen; its seeds are ignored. A failed audit is a result, not an error: FHH_OK with the ok bytes
+ * (1 ok, 0 not) and the report. Refusals (FHH_E_ARG, nothing written): NULL src / rep, what fhh_gen_keys_ball
+ * refuses in a source, data_len >= 2^18, and a point whose right bound carries out of bit L (found by the kernel;
+ * the message names the lowest (client, dim)).
+ *
+ * Multi-device ctxs (both, over the same devices) audit shard by shard, each its own clients: ok is concatenated,
+ * n_checks and n_bad_clients are summed, the first failure is the one of the lowest global client index.
+ * fhh_audit_keys_ball_device leaves the ok bytes in device memory instead (one-GPU ctxs only: FHH_E_ARG on a
+ * multi-device ctx, use fhh_shard_ctx): a buffer owned by ctx0, valid until its next audit, fhh_reset or
+ * fhh_destroy, and usable as a mask row of fhh_retain_clients_device.
+ *
+ * The first failure is the lowest in the order (client, dim, side, probe, level); got is the reconstructed bit
+ * there, expected the rule's. */
+typedef struct fhh_audit_report {
+    uint64_t n_checks;       /* comparisons made: n 2 d 5 L */
+    uint64_t n_bad_clients;  /* clients with ok = 0 */
+    uint64_t first_client;   /* UINT64_MAX if none; then the fields below are 0 */
+    uint32_t first_dim, first_side, first_probe, first_level;
+    uint32_t got, expected;
+} fhh_audit_report;
+int fhh_audit_keys_ball(fhh_ctx* ctx0, fhh_ctx* ctx1, uint64_t n, const fhh_ball_src* src, uint8_t* ok /* host [n], may be NULL */,
+                        fhh_audit_report* rep);
+int fhh_audit_keys_ball_device(fhh_ctx* ctx0, fhh_ctx* ctx1, uint64_t n, const fhh_ball_src* src,
+                               const uint8_t** ok_dev, fhh_audit_report* rep);
+/* The host arithmetic of the probes, no device call (like fhh_ball_bounds): probes [n][d][5][L], a byte 0/1 per bit,
+ * MSB first. *bad (may be NULL) = the lowest c n_dims + j whose right bound carries out, UINT64_MAX if none; a carry
+ * out returns FHH_E_ARG with nothing else written. The other refusals are those of a source. */
+int fhh_audit_probes(uint32_t n_dims, uint32_t data_len, uint64_t n, const fhh_ball_src* src, uint8_t* probes,
+                     uint64_t* bad);
+/* The launch arithmetic, no device call: an item is one wave's 64 clients of one key (2 n_dims ceil(n / 64) items),
+ * dealt grid-stride to min(ceil(items / 16), grid_blocks) workgroups of 16 waves; trips = ceil(items / waves),
+ * last_trip_items = items - (trips - 1) waves; aes_blocks = n 2 d 2 5 L (both servers' walks), n_checks = n 2 d 5 L.
+ * Any output may be NULL. FHH_E_ARG for n = 0, n_dims outside 1..4, data_len = 0, grid_blocks = 0. */
+int fhh_audit_plan(uint32_t n_dims, uint32_t data_len, uint64_t n, uint64_t grid_blocks, uint64_t* items,
+                   uint64_t* waves, uint64_t* trips, uint64_t* last_trip_items, uint64_t* aes_blocks,
+                   uint64_t* n_checks);
+/* Diagnostics of ctx0's last audit: the kernel's time (HIP events; a multi-device ctx: the slowest shard's). */
+int fhh_audit_timing(const fhh_ctx* ctx, double* ms);
+/* The seeds' side of ctx0's last audit. No compared bit depends on a seed (expand_dir's control bits are constants,
+ * prg.rs:97-104), so the ok bytes cannot see a wrong root seed or CorWord seed. The walks carry the seeds anyway,
+ * and a walk that has left its key's path (t0 == t1 after level L) must end with both servers' seeds equal:
+ * *n_diverged = the (client, dim, side, probe) walks for which that failed (a multi-device ctx: summed). */
+int fhh_audit_seed_check(const fhh_ctx* ctx, uint64_t* n_diverged);
+
 /* ---- one KeyCollection over several GPUs (north_star) -----------------------
  * KeyCollection::new on n_devices GPUs: one collection whose clients are sharded over the devices
  * (devices[k] may repeat — two shards on one GPU run the same code on a one-GPU box). At
