@@ -66,6 +66,7 @@ EXPORTS = [
     "fhh_party_set_server", "fhh_party_role_plan", "fhh_party_negate",
     "fhh_audit_keys_ball", "fhh_audit_keys_ball_device", "fhh_audit_probes", "fhh_audit_plan", "fhh_audit_timing",
     "fhh_audit_seed_check",
+    "fhh_join_clients_bincode", "fhh_join_plan", "fhh_join_timing",
 ]
 
 
@@ -124,7 +125,7 @@ class FhhSimConfig(ctypes.Structure):
 
 SOURCES = ("fhh_kernels.hip", "fhh_bincode_out.hip", "fhh_leader_requests.hip", "fhh_audit.hip", "fhh_retain.hip", "fhh_retain_mask.hip", "fhh_sketch.hip", "fhh_gc.hip", "fhh_ot.hip",
            "fhh_loop.hip", "fhh_microbench.hip", "fhh_host.cpp", "fhh_keys_io.cpp", "fhh_retain.cpp", "fhh_ball.cpp",
-           "fhh_audit.cpp",
+           "fhh_audit.cpp", "fhh_join.cpp",
            "fhh_sim_crawl.cpp", "fhh_sketch_host.cpp",
            "fhh_gcot.cpp", "fhh_gcot_harness.cpp", "fhh_group.cpp", "fhh_comm.cpp", "fhh_base_ot.cpp")
 
@@ -386,6 +387,9 @@ def lib():
         "fhh_retain_clients_device": (i, [vp, vp, u64, u32, u64, u64p]),
         "fhh_retain_plan_device": (i, [vp, vp, u64, u32, u64, u64p, u32p]),
         "fhh_retain_mask_timing": (i, [vp, P(ctypes.c_double)]),
+        "fhh_join_clients_bincode": (i, [vp, u8p, u64]),
+        "fhh_join_plan": (i, [u32, u32, u64, u64, u32p, u64, u64p, u64p, u64p, u64p, u64p, u64p, u64p, u64p, u64p]),
+        "fhh_join_timing": (i, [vp, P(ctypes.c_double), u64p]),
         "fhh_tree_crawl": (i, [vp, u64p, u64p]),
         "fhh_tree_crawl_last": (i, [vp, u64p, u64p]),
         "fhh_node_sums_fe": (i, [vp, u64p, u64p]),

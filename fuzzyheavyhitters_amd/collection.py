@@ -309,6 +309,38 @@ class KeyCollection:
         self._chk(lib().fhh_retain_timing(self._h, ms, by))
         return (ms[0], ms[1]), (int(by[0]), int(by[1]))
 
+    def join_clients_bincode(self, request: bytes):
+        """One `add_keys` request (the framing of `add_keys_bincode_append`) whose clients join a crawl in progress
+        (fhh_join_clients_bincode): the collection must have a frontier (after `tree_init`, `tree_init_at`, a prune
+        or `sim_crawl`). Afterwards it holds the old clients followed by the joiners, at the same frontier, as a
+        fresh collection of all of them brought there with `tree_init_at(frontier_paths())` would; only the joiners'
+        keys are walked. Both servers call it with their halves of the same batch. A refused batch raises and leaves
+        the collection as it was."""
+        buf = np.frombuffer(bytes(request), np.uint8) if not isinstance(request, np.ndarray) else \
+            np.ascontiguousarray(request, np.uint8)
+        self._chk(lib().fhh_join_clients_bincode(self._h, ptr(buf) if buf.size else None, buf.size))
+
+    @staticmethod
+    def join_plan(n_dims: int, depth: int, n: int, m: int, n_unique, grid_blocks: int) -> dict:
+        """fhh_join_plan (host arithmetic, no GPU): the walk of m clients joining n at a frontier of `depth` levels
+        with n_unique[j] live entries in dim j, on at most grid_blocks workgroups — first_word, first_mask, words,
+        new_nw, items, waves, trips, last_trip_items, aes_blocks."""
+        names = ("first_word", "first_mask", "words", "new_nw", "items", "waves", "trips", "last_trip_items",
+                 "aes_blocks")
+        nu = np.ascontiguousarray(n_unique, np.uint32).reshape(-1)
+        v = [ctypes.c_uint64() for _ in names]
+        check(lib().fhh_join_plan(n_dims, depth, n, m, ptr(nu, u32p) if nu.size else None, grid_blocks,
+                                  *[ctypes.byref(x) for x in v]))
+        return {k: int(x.value) for k, x in zip(names, v)}
+
+    def join_timing(self):
+        """((re-pitch ms, decode ms, walk ms), re-pitch bytes read plus written) of the last join_clients_bincode
+        that ran its kernels here (HIP events)."""
+        ms = (ctypes.c_double * 3)()
+        by = (ctypes.c_uint64 * 1)()
+        self._chk(lib().fhh_join_timing(self._h, ms, by))
+        return (ms[0], ms[1], ms[2]), int(by[0])
+
     def set_client_base(self, base: int):
         self._chk(lib().fhh_set_client_base(self._h, base))
 

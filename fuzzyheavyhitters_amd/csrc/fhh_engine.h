@@ -2,6 +2,7 @@
 //   fhh_host.cpp         one server's KeyCollection on one GPU (the engine core and its C ABI)
 //   fhh_keys_io.cpp      add_keys requests in bincode: decode, append and export
 //   fhh_retain.cpp       fhh_retain_clients: the collection compacted to the survivors of a keep mask
+//   fhh_join.cpp         fhh_join_clients_bincode: an add_keys batch joins a ctx that has a frontier
 //   fhh_sim_crawl.cpp    the in-process two-server harness: fhh_sim_*, the device-resident level loop
 //   fhh_sketch_host.cpp  sketch + Beaver verification wrappers
 //   fhh_group.cpp        one KeyCollection over several GPUs: clients sharded in 64-client words,
@@ -168,6 +169,10 @@ struct fhh_ctx {
     // scan, emit; HIP events), kept from call to call
     DevBuf keep_scan, keep_stage;
     double keep_ms[2] = {0, 0};
+    // the last fhh_join_clients_bincode that ran its kernels here: re-pitch, decode and walk time (HIP events) and
+    // the bytes the re-pitch read plus wrote (fhh_join_timing)
+    double join_ms[3] = {0, 0, 0};
+    uint64_t join_bytes = 0;
     DimTable tab[kMaxDims];
 
     Phase phase = Phase::kNoInit;
@@ -402,7 +407,19 @@ void retain_commit(fhh_ctx* ctx, RetainStage& st);   // host only: cannot fail
 // the survivors' records of add_keys-layout host vectors
 void retain_host_keys(const fhh_ctx* ctx, const uint32_t* src, uint64_t n2, RetainStage& st);
 
+// ---- fhh_join.cpp ----------------------------------------------------------------------------
+// fhh_join_clients_bincode on a one-GPU ctx, in the steps a multi-device ctx drives for its last shard: the
+// states it refuses, the request's framing (*m clients, their records from req + 8 on), and the join of m records
+// (every refusal and failure leaves the ctx as it was)
+int join_check_state(fhh_ctx* ctx);
+// n + m clients are a count the engine holds: at most 2^32 - 2, so that every client index and the count itself
+// stay below the u32 all-ones word
+inline bool join_count_fits(uint64_t n, uint64_t m) { return !(n >> 32) && !(m >> 32) && n + m < 0xFFFFFFFFull; }
+int join_parse(fhh_ctx* ctx, const uint8_t* req, uint64_t len, uint64_t* m);
+int join_one(fhh_ctx* ctx, uint64_t m, const uint8_t* recs);
+
 // ---- fhh_group.cpp (multi-device ctx) --------------------------------------------------------
+int group_join_clients_bincode(fhh_ctx* g, const uint8_t* req, uint64_t len);
 int group_retain_clients(fhh_ctx* g, const uint8_t* keep, uint64_t n);
 int group_retain_clients_device(fhh_ctx* g, const uint8_t* keep_dev, uint64_t n, uint32_t n_rows, uint64_t row_stride,
                                 uint64_t* n_kept);

@@ -843,6 +843,67 @@ int group_retain_clients_device(fhh_ctx* g, const uint8_t* keep_dev, uint64_t n,
     return FHH_OK;
 }
 
+// fhh_join_clients_bincode on a multi-device ctx: the joiners' global indices follow the last client, so the whole
+// batch lands on the last shard, whose range grows (the shards are then no longer balanced as fhh_shard_plan cuts
+// them; nothing is moved between devices). A last shard that a retain left empty takes the batch as its only keys
+// and is brought to the group's frontier as fhh_tree_init_at brings a shard there.
+int group_join_clients_bincode(fhh_ctx* g, const uint8_t* req, uint64_t len) {
+    Group& G = *g->group;
+    fhh_ctx* lead = group_lead(g);
+    if (!lead) {
+        if (g->h_n) return g->fail(FHH_E_STATE, "join_clients_bincode: no frontier yet (before fhh_tree_init clients are "
+                                                "added with fhh_add_keys_bincode_append or fhh_add_keys)");
+        return g->fail(FHH_E_STATE, "join_clients_bincode: the ctx holds no keys");
+    }
+    for (size_t k : G.active()) {
+        const int rc = join_check_state(G.shards[k]);
+        if (rc) return shard_fail(g, k, rc);
+    }
+    uint64_t m = 0, n = 0;
+    int rc = join_parse(g, req, len, &m);
+    if (rc) return rc;
+    group_num_clients(g, &n);
+    if (!join_count_fits(n, m))
+        return g->fail(FHH_E_ARG, "join_clients_bincode: " + std::to_string(n) + " + " + std::to_string(m) +
+                                      " clients do not fit the engine's u32 client indices");
+    const size_t k = G.shards.size() - 1;
+    fhh_ctx* s = G.shards[k];
+    if (G.count[k]) {
+        rc = join_one(s, m, req + 8);
+        if (rc) return shard_fail(g, k, rc);
+    } else {
+        uint64_t F = 0;
+        uint32_t depth = 0;
+        rc = fhh_frontier_paths(lead, &F, &depth, nullptr);
+        if (rc) return g->fail(rc, lead->err);
+        std::vector<uint8_t> paths((size_t)F * g->d * depth);
+        rc = fhh_frontier_paths(lead, &F, &depth, paths.data());
+        if (rc) return g->fail(rc, lead->err);
+        FrontierPlan plan;
+        std::string why;
+        if (!frontier_plan(g->d, depth, F, paths.data(), plan, &why)) return g->fail(FHH_E_STATE, "join_clients_bincode: " + why);
+        rc = add_keys_bincode_records(s, m, req + 8);
+        if (!rc) rc = tree_init_at_planned(s, plan, F, depth, paths.data());
+        if (rc) {
+            const std::string msg = s->err;
+            (void)fhh_reset(s);   // the empty-shard state again
+            s->err = msg;
+            return shard_fail(g, k, rc);
+        }
+        s->join_ms[0] = s->join_ms[1] = s->join_ms[2] = 0;
+        s->join_bytes = 0;
+        G.base[k] = n;
+    }
+    G.count[k] += m;
+    // the collection is now a placed one of n + m clients, whatever path its keys came by
+    G.appended = false;
+    G.reserved = G.app_n = 0;
+    set_bases(G);
+    for (int i = 0; i < 3; i++) g->join_ms[i] = s->join_ms[i];
+    g->join_bytes = s->join_bytes;
+    return ensure_comms(g);
+}
+
 fhh_ctx* group_shard0(const fhh_ctx* g) { return g->group->shards[0]; }
 
 fhh_ctx* group_lead(const fhh_ctx* g) {

@@ -334,9 +334,51 @@ struct EvalPathsArgs {
     uint64_t total_items;
 };
 
+// k_join_paths (fhh_join_clients_bincode): k_eval_paths' walk on the words [w_first, w_first + words) of the layout
+// only — the clients that joined a ctx with a frontier. Job j's prefix e is the dim's e-th live entry and goes to
+// table entry rows[j][e]; an item is one of those words of one side of kEvalPathsP prefixes (job j has
+// 2 words ceil(n_prefixes / kEvalPathsP) items). In word w_first only the lanes of first_mask are written: the
+// others hold the states of clients that were there before.
+struct JoinPathsExtra {
+    const uint32_t* rows[kMaxDims];   // [n_prefixes] table entry of each prefix
+    uint64_t first_mask;              // lanes >= n % 64 (all ones when n % 64 == 0)
+    uint32_t w_first;                 // n / 64
+    uint32_t words;                   // new nw - w_first
+};
+// The launch of k_join_paths (fhh_join_plan): n clients held, m joining, U[j] live entries of dim j, at most
+// grid_blocks workgroups of kAuditBlock (= k_eval_paths' 1024) threads
+struct JoinPlan {
+    uint64_t first_word, first_mask, words, new_nw, items, blocks, waves, trips, last_trip_items, aes_blocks;
+};
+__host__ __device__ inline JoinPlan join_plan(uint32_t d, uint32_t depth, uint64_t n, uint64_t m, const uint32_t* U,
+                                              uint64_t grid_blocks) {
+    const uint64_t wpb = 1024 / 64;
+    JoinPlan p;
+    p.first_word = n / 64;
+    p.first_mask = ~((n % 64) ? (1ull << (n % 64)) - 1 : 0ull);
+    p.new_nw = (n + m + 63) / 64;
+    p.words = p.new_nw - p.first_word;
+    p.items = 0;
+    uint64_t entries = 0;
+    for (uint32_t j = 0; j < d; j++) {
+        p.items += 2 * p.words * (((uint64_t)U[j] + kEvalPathsP - 1) / kEvalPathsP);
+        entries += U[j];
+    }
+    p.blocks = (p.items + wpb - 1) / wpb;
+    if (p.blocks > grid_blocks) p.blocks = grid_blocks;
+    p.waves = p.blocks * wpb;
+    p.trips = p.waves ? (p.items + p.waves - 1) / p.waves : 0;
+    p.last_trip_items = p.trips ? p.items - (p.trips - 1) * p.waves : 0;
+    p.aes_blocks = (uint64_t)depth * 2 * entries * m;
+    return p;
+}
+
 // ---- launch wrappers (fhh_kernels.hip); all asynchronous on `stream` ----
 // grid: at most this many workgroups (the persistent k_expand grid; the items are dealt grid-stride)
 hipError_t launch_eval_paths(const EvalPathsArgs& a, int grid, hipStream_t stream);
+// a.job[j].dst_* = the dim's current table at a.npad / a.nw, n_prefixes its live entries, dirs their directions;
+// a.total_items / item_begin by JoinPathsExtra's item count
+hipError_t launch_join_paths(const EvalPathsArgs& a, const JoinPathsExtra& x, int grid, hipStream_t stream);
 // seq: the counter's launch count (fhh_ctx::expand_seq), advanced per k_expand launch
 hipError_t launch_expand(const ExpandLaunch& a, int variant, int grid, uint32_t* work_counter, uint32_t* seq,
                          hipStream_t stream);

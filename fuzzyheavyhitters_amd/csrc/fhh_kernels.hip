@@ -906,7 +906,16 @@ hipError_t launch_init_tables(const uint4* root, const uint64_t* key_idx, uint32
 // k_expand's launch shape: 1024 threads share the 128 KiB of tables, 4 waves per SIMD; every item costs
 // the same, so the items are dealt grid-stride.
 // --------------------------------------------------------------------------------------
-__global__ __launch_bounds__(kExpandBlock, 1) void k_eval_paths(EvalPathsArgs a) {
+// Two forms of one body (as k_keygen's): kEvalAll is k_eval_paths, every word of the layout into entries
+// 0 .. n_prefixes - 1; kEvalJoin is k_join_paths (fhh_join_clients_bincode), the words [w_first, w_first + words)
+// only, prefix e into the table entry rows[e] (the dim's live list), and in the word the joiners share with the
+// clients already there (first_mask != ~0) only their lanes: the seed stores predicated, the t / y words merged
+// as (old & ~mask) | (new & mask), bincode_span.h's rule for the keys.
+// --------------------------------------------------------------------------------------
+constexpr int kEvalAll = 0;
+constexpr int kEvalJoin = 1;
+template <int FORM>
+__device__ __forceinline__ void eval_paths_body(const EvalPathsArgs& a, const JoinPathsExtra& x) {
     __shared__ uint32_t tbl[ExpandTab::kWords];
     for (int i = threadIdx.x; i < ExpandTab::kWords; i += kExpandBlock) tbl[i] = ExpandTab::word(c_T0.v, i);
     __syncthreads();
@@ -924,8 +933,14 @@ __global__ __launch_bounds__(kExpandBlock, 1) void k_eval_paths(EvalPathsArgs a)
         const EvalPathsJob& J = a.job[j];
         // item = (group * 2 + side) * nw + word: a workgroup's waves read neighbouring words of one CorWord row
         const uint64_t local = item - J.item_begin;
-        const uint32_t w = (uint32_t)(local % nw);
-        const uint32_t gs = (uint32_t)(local / nw);
+        uint32_t w, gs;
+        if constexpr (FORM == kEvalJoin) {
+            w = x.w_first + (uint32_t)(local % x.words);
+            gs = (uint32_t)(local / x.words);
+        } else {
+            w = (uint32_t)(local % nw);
+            gs = (uint32_t)(local / nw);
+        }
         const uint32_t s = gs & 1u, e0 = (gs >> 1) * P;
         const uint32_t c = w * 64 + lane;
         const size_t kk = 2 * j + s;
@@ -1001,15 +1016,38 @@ __global__ __launch_bounds__(kExpandBlock, 1) void k_eval_paths(EvalPathsArgs a)
         for (int p = 0; p < P; p++) {
             const uint32_t e = e0 + p;
             if (e < J.n_prefixes) {   // wave-uniform
-                const size_t row = (size_t)2 * e + s;
-                J.dst_seed[row * npad + c] = make_uint4(sd[p][0], sd[p][1], sd[p][2], sd[p][3]);
-                if (lane == 0) {
-                    J.dst_t[row * nw + w] = tw[p];
-                    J.dst_y[row * nw + w] = yw[p];
+                if constexpr (FORM == kEvalJoin) {
+                    const size_t row = (size_t)2 * uniform_load(x.rows[j], e) + s;
+                    const uint64_t own = w == x.w_first ? x.first_mask : ~0ull;   // the lanes this launch writes
+                    if ((own >> lane) & 1) J.dst_seed[row * npad + c] = make_uint4(sd[p][0], sd[p][1], sd[p][2], sd[p][3]);
+                    if (lane == 0) {
+                        uint64_t t = tw[p], y = yw[p];
+                        if (own != ~0ull) {
+                            t = (J.dst_t[row * nw + w] & ~own) | (t & own);
+                            y = (J.dst_y[row * nw + w] & ~own) | (y & own);
+                        }
+                        J.dst_t[row * nw + w] = t;
+                        J.dst_y[row * nw + w] = y;
+                    }
+                } else {
+                    const size_t row = (size_t)2 * e + s;
+                    J.dst_seed[row * npad + c] = make_uint4(sd[p][0], sd[p][1], sd[p][2], sd[p][3]);
+                    if (lane == 0) {
+                        J.dst_t[row * nw + w] = tw[p];
+                        J.dst_y[row * nw + w] = yw[p];
+                    }
                 }
             }
         }
     }
+}
+
+__global__ __launch_bounds__(kExpandBlock, 1) void k_eval_paths(EvalPathsArgs a) {
+    eval_paths_body<kEvalAll>(a, JoinPathsExtra{});
+}
+
+__global__ __launch_bounds__(kExpandBlock, 1) void k_join_paths(EvalPathsArgs a, JoinPathsExtra x) {
+    eval_paths_body<kEvalJoin>(a, x);
 }
 
 hipError_t launch_eval_paths(const EvalPathsArgs& a, int grid, hipStream_t stream) {
@@ -1018,6 +1056,16 @@ hipError_t launch_eval_paths(const EvalPathsArgs& a, int grid, hipStream_t strea
     const uint64_t blocks_needed = (a.total_items + wpb - 1) / wpb;
     const int g = (int)(blocks_needed < (uint64_t)grid ? blocks_needed : (uint64_t)grid);
     hipLaunchKernelGGL(k_eval_paths, dim3(g), dim3(kExpandBlock), 0, stream, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_join_paths(const EvalPathsArgs& a, const JoinPathsExtra& x, int grid, hipStream_t stream) {
+    if (a.total_items == 0) return hipSuccess;
+    if (x.words == 0 || (uint64_t)x.w_first + x.words > a.nw) return hipErrorInvalidValue;
+    const uint64_t wpb = kExpandBlock / 64;
+    const uint64_t blocks_needed = (a.total_items + wpb - 1) / wpb;
+    const int g = (int)(blocks_needed < (uint64_t)grid ? blocks_needed : (uint64_t)grid);
+    hipLaunchKernelGGL(k_join_paths, dim3(g), dim3(kExpandBlock), 0, stream, a, x);
     return hipGetLastError();
 }
 

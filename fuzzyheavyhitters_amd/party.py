@@ -305,7 +305,7 @@ def two_party_crawl(c0: KeyCollection, c1: KeyCollection, threshold: float, ncli
                     level_log: list | None = None, base_ot_every: str = "level",
                     base_ot_workers: int | None = None, base_ot_ahead: int = 8,
                     form: str = "table", ot_ss_k: int = 1, start_paths=None, roles: str = "fixed",
-                    server_busy: list | None = None) -> TwoPartyResult:
+                    server_busy: list | None = None, joins: dict | None = None) -> TwoPartyResult:
     """The leader's level loop (leader.rs:417-440) with the GC + OT of every level split between the
     two servers' ctxs (server 0 garbles / sends, server 1 evaluates / receives): crawl both, run the
     level's protocol through the channel, take each server's node sums from its own device
@@ -351,7 +351,23 @@ def two_party_crawl(c0: KeyCollection, c1: KeyCollection, threshold: float, ncli
     collections are told which server they are (`party_set_server`), so the node sums come out with the
     reference's sign and the leader's keep_values / final_values are unchanged. material "test" derives the
     second direction's material from prf_seed with a direction bit. `server_busy` (a list [server 0, server 1])
-    accumulates the wall seconds of each server's own fhh_gb_* / fhh_ev_* calls."""
+    accumulates the wall seconds of each server's own fhh_gb_* / fhh_ev_* calls.
+
+    `joins` (None: nobody joins): a dict level -> (req0, req1), the two servers' halves of one `add_keys` request
+    whose clients join before that level's crawl (`KeyCollection.join_clients_bincode` on c0 / c1). The levels
+    from there on count the joiners; the thresholds stay those computed from `nclients_total`, and the party
+    states are not rebuilt."""
+    if joins is not None:
+        if not isinstance(joins, dict):
+            raise TypeError(f"two_party_crawl: joins must be a dict level -> (req0, req1), not {type(joins).__name__}")
+        for lv, reqs in joins.items():
+            if isinstance(lv, bool) or not isinstance(lv, (int, np.integer)):
+                raise TypeError(f"two_party_crawl: joins key {lv!r} is not a level number")
+            if not isinstance(reqs, (tuple, list)) or len(reqs) != 2:
+                raise ValueError(f"two_party_crawl: joins[{lv}] must be the pair (req0, req1)")
+            for r in reqs:
+                if not isinstance(r, (bytes, bytearray, memoryview, np.ndarray)):
+                    raise TypeError(f"two_party_crawl: joins[{lv}] holds a {type(r).__name__}, not request bytes")
     if roles not in ROLE_MODES:
         raise ValueError(f"two_party_crawl: roles {roles!r}")
     role_mode = ROLE_MODES[roles]
@@ -376,6 +392,9 @@ def two_party_crawl(c0: KeyCollection, c1: KeyCollection, threshold: float, ncli
         if start_paths.shape[2] >= L:
             raise ValueError(f"two_party_crawl: start_paths of depth {start_paths.shape[2]} leave no level of {L} to run")
     lv0 = 0 if start_paths is None else start_paths.shape[2]
+    for lv in (joins or {}):
+        if not lv0 <= lv < L:
+            raise ValueError(f"two_party_crawl: joins[{lv}] is outside the levels {lv0} .. {L - 1} of this crawl")
     thr = max(1, int(threshold * n_total))
     thr_last = max(1, min(int(threshold * n_total), 0xFFFFFFFF))
     S = len(c0.shard_info()[0])
@@ -447,6 +466,14 @@ def two_party_crawl(c0: KeyCollection, c1: KeyCollection, threshold: float, ncli
             last = lv == L - 1
             if pool is not None and lv + base_ot_ahead < L:
                 submit(lv + base_ot_ahead)
+            if joins and lv in joins:
+                c0.join_clients_bincode(joins[lv][0])
+                c1.join_clients_bincode(joins[lv][1])
+                # the batch landed on the last pair of shards, which may have been empty until now
+                shard_clients = [a.num_clients() for a, _ in shards]
+                if pool is not None:
+                    for ahead in range(lv, min(L, lv + base_ot_ahead + 1)):
+                        submit(ahead)
             t0 = clock()
             C0, _ = (c0.tree_crawl_last if last else c0.tree_crawl)()
             C1, _ = (c1.tree_crawl_last if last else c1.tree_crawl)()

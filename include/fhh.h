@@ -467,6 +467,60 @@ int fhh_retain_plan_device(fhh_ctx* ctx, const uint8_t* keep_dev, uint64_t n, ui
                            uint64_t* n_kept, uint32_t* src);
 int fhh_retain_mask_timing(const fhh_ctx* ctx, double* ms);
 
+/* Clients that join a crawl in progress (row k; past the reference, whose add_key after tree_init leaves
+ * key_states too short for the next crawl, server.rs:71-77). `req` is one add_keys request in the framing of
+ * fhh_add_keys_bincode_append (a u64 m, then m client records); the ctx must be in the frontier phase (after
+ * fhh_tree_init, fhh_tree_init_at, a prune or fhh_sim_crawl) and holds n clients on the device.
+ * Afterwards the ctx is a collection of the n + m clients, the old ones first and the joiners in request order, at
+ * the same frontier: fhh_num_clients, fhh_export_keys(_bincode), fhh_export_states of the current frontier and
+ * every later crawl, share plane, sum, party message size and final share are those of a fresh ctx given all
+ * n + m keys and brought there with fhh_tree_init_at(fhh_frontier_paths). Unchanged: the frontier, its history and
+ * level, frontier_last and its recorded values, client_base, the variant and grid settings, a party state between
+ * levels (its base-OT session counters included). Sums already returned for earlier levels, and the recorded
+ * frontier_last values, do not include the joiners (as those after fhh_retain_clients still include the dropped).
+ * stats.aes_blocks grows by depth * 2 * sum_j U_j * m (U_j = dim j's live entries): only the joiners' keys are
+ * walked, by k_join_paths, k_eval_paths' second form, over the 64-client words [n / 64, ceil((n + m) / 64)). The
+ * directions of the live entries come from the ctx's own history, not from the caller.
+ * Layout: npad = 64 ceil((n + m) / 64) afterwards, as after every other path. Where the word count does not change
+ * the joiners take the free lanes of the last word in place and nothing is copied. Where it grows, the key buffers
+ * and the current half of every dim's table (its live entries only, compacted to rows 0 .. U_j - 1) are copied to
+ * buffers of the new stride: one copy of the key store per call, which is why joins are meant for batches, not
+ * single clients. Never in place: peak extra device memory = the new key buffers and tables (old plus new are
+ * both live until the stream has drained), then the old ones are freed and the unused half of every table pair is
+ * released, to be re-sized by the next crawl.
+ * FHH_E_STATE before any init (fhh_add_keys_bincode_append / fhh_add_keys add clients there), while a crawl's
+ * children are pending (prune first) and with no keys. FHH_E_ARG for a NULL req, a len other than 8 + m * R, m = 0,
+ * n + m >= 2^32 - 1 (2^32 - 2 clients are the most a ctx holds) and every malformed field fhh_add_keys_bincode refuses, with its message text (a bool byte > 1, a
+ * cor_words length, dims per client). Every refusal, and FHH_E_NOMEM (every destination is allocated before the
+ * first launch), leaves the ctx exactly as it was: a growing join decodes into the new buffers, the walk starts
+ * only after the decode's error word has been read, and a refused batch that shared the last word has its lanes
+ * zeroed again.
+ * On a multi-device ctx the joiners follow the last client, so the whole batch lands on the last shard, whose range
+ * grows: fhh_shard_info then no longer reports fhh_shard_plan's ranges (as after a retain), and the shards are no
+ * longer balanced — a level costs what its largest shard costs. Nothing is rebalanced. A last shard that a retain
+ * left empty takes the batch as its only keys and walks them to the group's frontier as fhh_tree_init_at does.
+ *
+ * fhh_join_plan is the host arithmetic of the walk's launch, no device call (like fhh_audit_plan): n clients
+ * held, m joining, n_unique[j] = U_j, at most grid_blocks workgroups of 16 waves. first_word = n / 64, first_mask =
+ * the lanes >= n % 64 of that word (all ones when n % 64 = 0), new_nw = ceil((n + m) / 64), words = new_nw -
+ * first_word, items = sum_j 2 words ceil(U_j / 4), waves / trips / last_trip_items as fhh_audit_plan's, aes_blocks =
+ * depth * 2 * sum_j U_j * m. Any output may be NULL. FHH_E_ARG (nothing written) for m = 0, n = 0, n + m >= 2^32 - 1,
+ * n_dims outside 1..4, a zero U_j, a NULL n_unique or grid_blocks = 0.
+ *
+ * fhh_join_timing is for diagnostics only (tools/join_time.py): ms[3] = the re-pitch, decode and walk kernels' time
+ * (HIP events) of the last join that ran on this ctx (a multi-device ctx: its last shard's), bytes[1] = what the
+ * re-pitch read plus wrote (0 where the word count did not change).
+ * Unmeasured so far: tools/join_time.py (configs[1], depth 256, 1 000 and 50 000 joiners against the export ->
+ * add_keys -> tree_init_at route and against tree_init_at of all n + m clients) has not been run, so neither the
+ * expectation that the walk costs about m / (n + m) of that tree_init_at plus one word nor the re-pitch's rate
+ * beside the retain gather's 5.05 TB/s is confirmed or refuted. */
+int fhh_join_clients_bincode(fhh_ctx* ctx, const uint8_t* req, uint64_t len);
+int fhh_join_plan(uint32_t n_dims, uint32_t depth, uint64_t n, uint64_t m, const uint32_t* n_unique /* [n_dims] */,
+                  uint64_t grid_blocks, uint64_t* first_word, uint64_t* first_mask, uint64_t* words,
+                  uint64_t* new_nw, uint64_t* items, uint64_t* waves, uint64_t* trips, uint64_t* last_trip_items,
+                  uint64_t* aes_blocks);
+int fhh_join_timing(const fhh_ctx* ctx, double* ms /* [3]: repitch, decode, walk */, uint64_t* bytes /* [1]: repitch read+written */);
+
 /* Frontier expansion of tree_crawl (collect.rs:379-418): evaluates every client's 2d keys
  * one level for every child of every frontier node. *n_children = C. share_planes (may be
  * NULL) receives [C][2d][nw] u64 — the GC input of collect.rs:415-418.
